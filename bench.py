@@ -2,7 +2,7 @@
 """Benchmark: device-resident batched CRC32C on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5]
-                    [--scaling weak|strong]
+                    [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 One "step" = one batch CRC32C launch over this rank's whole synthetic batch,
 inputs already resident in HBM.  Default workload (N=1 headline, BASELINE.json
@@ -25,11 +25,14 @@ Before the W warmup steps a `settle` phase runs back-to-back launches until
 the chip's idle->busy power transient has passed (reported in the JSON line,
 separate from `warmup`; see settle()).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
-`roofline` (kernel launch duration by HIP events on the launch stream vs the
-8 TB/s HBM3E peak) and `cpu_baseline` (the CPU oracle — a restatement of the
-reference's SSE4.2 `extend_hw`, crc32c.rs:86-118 — timed single-threaded on
-this host over a bounded sample of the same blocks).
+Prints ONE JSON line on rank 0.  A plain run does only what `value` needs: set-up, settle, warmup, the K timed steps, the
+line (and, with `--dump-outputs DIR`, the CRCs the last timed step produced).
+`--full` adds, as before: `roofline` (kernel launch duration by HIP events on
+the launch stream vs the 8 TB/s HBM3E peak, in a second pass of K steps, with
+a child rocprofv3 traffic pass), the oracle parity samples, `cpu_baseline`
+(the CPU oracle — a restatement of the reference's SSE4.2 `extend_hw`,
+crc32c.rs:86-118 — timed single-threaded on this host over a bounded sample of
+the same blocks) and the `c5_strong` sub-record.
 """
 import argparse
 import ctypes
@@ -109,7 +112,15 @@ def parse():
                    help="auto: the default C3 line also times BASELINE configs[4] (64 GiB of 4 KiB blocks split "
                         "across the ranks) as its `c5_strong` sub-record")
     p.add_argument("--traffic", default="auto", choices=["auto", "off"],
-                   help="auto: measure roofline.traffic in a child rocprofv3 --pmc FETCH_SIZE pass")
+                   help="auto: measure roofline.traffic in a child rocprofv3 --pmc FETCH_SIZE pass (--full)")
+    p.add_argument("--full", action="store_true",
+                   help="the headline line with everything beside it: the per-launch HIP-event pass (`roofline`), "
+                        "the oracle parity samples, `cpu_baseline`, the rocprofv3 traffic pass and the `c5_strong` "
+                        "sub-record.  Without it the run settles, warms up, times the K steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the CRCs the last step left in `out` (what a caller of the "
+                        "timed API receives) to DIR/crc32c.npy as float64 (crc32c.rankR.npy per rank when N > 1); "
+                        "more than 4 Mi buffers: a fixed seeded sample, its indices in crc32c_index*.npy")
     return p.parse_args()
 
 
@@ -1540,6 +1551,8 @@ def main():
         raise SystemExit("--gpus must be >= 1")
     if single and args.gpus > 1:
         raise SystemExit(f"--{single[0].replace('_', '-')} is a single-GPU diagnostic; run it with --gpus 1")
+    if args.dump_outputs and (single or args.variants):
+        raise SystemExit("--dump-outputs writes the batch CRC32C line's outputs; it does not go with a diagnostic mode")
     from lvgpu import shard
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without torchrun: start the N ranks here
@@ -1623,12 +1636,14 @@ def main():
     # (lvgpu.shard.timed_steps, the code the gloo test drives).  A timestamp
     # event between launches costs ~3 % of the step time on MI355X, so the
     # per-launch HIP events for roofline.achieved are taken in a second pass
-    # of the same K steps, right after, on the launch stream.
-    head = timed_line(torch, step, stream, args, dist, backend, dev, chunk=20, active=n > 0)
+    # of the same K steps, right after, on the launch stream (--full only).
+    head = timed_line(torch, step, stream, args, dist, backend, dev, chunk=20, active=n > 0, events=args.full)
     kern_ms = head["kern_ms"]
-    kern_avg_ms = sum(kern_ms) / len(kern_ms)
+    kern_avg_ms = sum(kern_ms) / len(kern_ms) if kern_ms else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, n, rank, world)
     own = rank_record(torch, dev, rank, local, nbytes, args.steps, head["timing"], kern_avg_ms)
-    if n > 0:  # every rank checks a sample of its own batch against the oracle
+    if n > 0 and args.full:  # every rank checks a sample of its own batch against the oracle
         if args.scaling == "weak":
             own["parity_sample"] = rank_sample_check(off, ln, out, n, PAYLOAD_SEED ^ (shard_rank * 0x9E3779B9))
         elif args.workload in ("c3", "c5"):  # a uniform global batch: its global offsets
@@ -1640,7 +1655,6 @@ def main():
     agg = shard.aggregate(per_rank, args.steps, head["timing"].own_max)
     agg_b = shard.aggregate(per_rank, args.steps, head["timing"].barrier_max)
     value = agg["GiB_per_s"]
-    achieved_gbs = nbytes / (kern_avg_ms * 1e-3) / 1e9
     kernel = lvgpu.last_kernel()
 
     # BASELINE configs[4]: one global batch of 64 GiB of
@@ -1660,14 +1674,29 @@ def main():
     result = None
     if rank == 0:
         cpu = None
-        if args.cpu_seconds > 0:
+        if args.full and args.cpu_seconds > 0:
             cpu, crcs, k = cpu_baseline(torch, arena, off, ln, args.cpu_seconds)
             got = out[:k].cpu().numpy().view("uint32")
             if not (got == crcs).all():
                 raise SystemExit("bench parity check failed: GPU CRCs differ from the oracle on the sample")
-        traffic, tsrc = (None, "not collected")
-        if args.traffic == "auto":
-            traffic, tsrc = measure_traffic(args, shard_rank, shard_world)
+        roofline = None
+        if args.full:
+            traffic, tsrc = (None, "not collected")
+            if args.traffic == "auto":
+                traffic, tsrc = measure_traffic(args, shard_rank, shard_world)
+            achieved_gbs = nbytes / (kern_avg_ms * 1e-3) / 1e9
+            roofline = {"bound": "hbm", "achieved": round(achieved_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved_gbs / HBM_PEAK_GBS, 4),
+                        "traffic": None if traffic is None else round(traffic), "traffic_source": tsrc,
+                        "kernel": "lvk::" + kernel if strided else
+                                  "lv_crc32c_batch_device step: lvk::sort_{hist,scan,scatter} + "
+                                  "lvk::crc32c_classes_kernel",
+                        "kernel_ms_avg": round(kern_avg_ms, 4),
+                        "kernel_ms_min": round(kern_ms[0], 4),
+                        "kernel_ms_p50": round(kern_ms[len(kern_ms) // 2], 4),
+                        "kernel_ms_max": round(kern_ms[-1], 4), "bytes_per_launch": nbytes,
+                        "timing": "HIP events around each of K launches on the launch stream, in a second "
+                                  "pass of the K timed steps"}
         result = {
             "metric": METRIC, "value": round(value, 2), "unit": "GiB/s", "n_gpus": world,
             "world_size": world,
@@ -1688,18 +1717,8 @@ def main():
                                             f"no collective)")},
             "hbm_peak_frac": round(value * 2**30 / world / 1e9 / HBM_PEAK_GBS, 4),
             "settle": head["settle"],
-            "roofline": {"bound": "hbm", "achieved": round(achieved_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved_gbs / HBM_PEAK_GBS, 4),
-                         "traffic": None if traffic is None else round(traffic), "traffic_source": tsrc,
-                         "kernel": "lvk::" + kernel if strided else
-                                   "lv_crc32c_batch_device step: lvk::sort_{hist,scan,scatter} + "
-                                   "lvk::crc32c_classes_kernel",
-                         "kernel_ms_avg": round(kern_avg_ms, 4),
-                         "kernel_ms_min": round(kern_ms[0], 4),
-                         "kernel_ms_p50": round(kern_ms[len(kern_ms) // 2], 4),
-                         "kernel_ms_max": round(kern_ms[-1], 4), "bytes_per_launch": nbytes,
-                         "timing": "HIP events around each of K launches on the launch stream, in a second "
-                                   "pass of the K timed steps"},
+            "full": args.full,  # False: roofline, cpu_baseline, c5_strong and the parity samples were not run
+            "roofline": roofline,
             "cpu_baseline": cpu,
             "per_gpu": per_rank,
             "load_imbalance": round(agg["imbalance"], 4),
@@ -1713,9 +1732,10 @@ TIMING_NOTE = ("value = bytes of all ranks x steps / max over ranks of each rank
                "sync -> K steps -> sync); *_barrier_inclusive: the same up to the end of the closing barrier")
 
 
-def timed_line(torch, step, stream, args, dist, backend, dev, chunk, active=True):
-    """settle -> warmup -> the K timed steps (shard.timed_steps) -> a second
-    pass of K steps with a HIP event pair around each launch on `stream`."""
+def timed_line(torch, step, stream, args, dist, backend, dev, chunk, active=True, events=True):
+    """settle -> warmup -> the K timed steps (shard.timed_steps) -> with
+    `events`, a second pass of K steps with a HIP event pair around each
+    launch on `stream` (`kern_ms`; None without it)."""
     from lvgpu import shard
     settle_info = settle(torch, step, stream, chunk=chunk) if args.settle and active else None
     for _ in range(args.warmup):
@@ -1724,6 +1744,8 @@ def timed_line(torch, step, stream, args, dist, backend, dev, chunk, active=True
     tm = shard.timed_steps(
         step, args.steps, torch.cuda.synchronize, dist,
         lambda x: torch.tensor(x, dtype=torch.float64, device=dev if backend == "nccl" else "cpu"))
+    if not events:
+        return {"settle": settle_info, "timing": tm, "kern_ms": None}
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     torch.cuda.synchronize()
     for s, e in evs:
@@ -1738,25 +1760,27 @@ def timed_line(torch, step, stream, args, dist, backend, dev, chunk, active=True
 
 
 def rank_record(torch, dev, rank, local, nbytes, steps, tm, kern_avg_ms):
-    """This rank's entry of `per_gpu` (SURVEY 8e per-GPU figures)."""
+    """This rank's entry of `per_gpu` (SURVEY 8e per-GPU figures); the kernel
+    figures are None when the per-launch event pass was not run."""
     props = torch.cuda.get_device_properties(dev)
+    kern_gbs = None if kern_avg_ms is None else nbytes / (kern_avg_ms * 1e-3) / 1e9
     return {"rank": rank, "device": local,
             "pci_bus_id": f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}",
             "gpu_uuid": str(getattr(props, "uuid", "")), "hostname": socket.gethostname(),
             "payload_bytes": nbytes,
             "own_ms_per_step": round(tm.own / steps * 1e3, 4),
             "GiB_per_s": round(nbytes * steps / 2**30 / tm.own, 2),
-            "kernel_GB_per_s": round(nbytes / (kern_avg_ms * 1e-3) / 1e9, 1),
-            "frac_of_8TBps": round(nbytes / (kern_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+            "kernel_GB_per_s": None if kern_gbs is None else round(kern_gbs, 1),
+            "frac_of_8TBps": None if kern_gbs is None else round(kern_gbs / HBM_PEAK_GBS, 4)}
 
 
 C5_BLOCKS = 16777216  # BASELINE configs[4]: 64 GiB of 4 KiB blocks
 
 
 def c5_wanted(args):
-    """The C5 sub-record rides in the default line: the C3 weak headline over
+    """The C5 sub-record rides in the default --full line: the C3 weak headline over
     the strided API, not a --as-rank replay (the PMC child) and not asked off."""
-    return (args.c5_strong == "auto" and args.workload == "c3" and args.scaling == "weak"
+    return (args.full and args.c5_strong == "auto" and args.workload == "c3" and args.scaling == "weak"
             and args.api == "strided" and args.as_world == 1 and not args.blocks and not args.group)
 
 
@@ -1809,6 +1833,26 @@ def c5_strong_record(torch, lvgpu, args, dist, backend, dev, rank, local, world,
             "per_gpu": per, "load_imbalance": round(agg["imbalance"], 4),
             "parity": "every rank's first and last 8 blocks vs the oracle over host bytes generated at the "
                       "same global offsets"}
+
+
+DUMP_MAX = 4 << 20  # values per array: 32 MiB of float64 (+ as much again for a sample's indices)
+
+
+def dump_outputs(path, out, n, rank, world):
+    """--dump-outputs: this rank's CRCs of the last timed step (`out[:n]`,
+    what the caller of the timed API receives) as float64 (exact for a u32) in
+    DIR/crc32c.npy (crc32c.rankR.npy when N > 1).  More than DUMP_MAX
+    buffers: the CRCs at DUMP_MAX sorted indices drawn with a fixed seed,
+    the indices beside them in crc32c_index*.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f".rank{rank}"
+    got = out[:n].cpu().numpy().view(np.uint32)
+    if n > DUMP_MAX:
+        idx = np.sort(np.random.default_rng(0x0D0D).choice(n, size=DUMP_MAX, replace=False))
+        np.save(os.path.join(path, f"crc32c_index{tag}.npy"), idx.astype(np.float64))
+        got = got[idx]
+    np.save(os.path.join(path, f"crc32c{tag}.npy"), got.astype(np.float64))
 
 
 def rank_sample_check(off, ln, out, n, seed, sh=None, k=8):

@@ -3,6 +3,8 @@ kernel-name classification its VALU pass uses."""
 import importlib.util
 import os
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -98,3 +100,63 @@ def test_parse_cpulist():
     assert b.parse_cpulist("0-3,8,10-11\n") == {0, 1, 2, 3, 8, 10, 11}
     assert b.parse_cpulist("64-127,192-255") == set(range(64, 128)) | set(range(192, 256))
     assert b.parse_cpulist("") == set()
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: float64 arrays exact for a u32; over DUMP_MAX values a
+    fixed sorted sample with its indices, the same from call to call; one file
+    per rank when N > 1."""
+    import numpy as np
+    import torch
+    b = _bench()
+    crcs = np.array([0, 1, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF, 12345], dtype=np.uint32)
+    out = torch.from_numpy(crcs.view(np.int32).copy())
+    b.dump_outputs(str(tmp_path / "a"), out, 5, 0, 1)
+    got = np.load(tmp_path / "a" / "crc32c.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, crcs[:5].astype(np.float64))
+    b.dump_outputs(str(tmp_path / "a"), out, 6, 1, 2)
+    assert np.array_equal(np.load(tmp_path / "a" / "crc32c.rank1.npy"), crcs.astype(np.float64))
+    b.DUMP_MAX = 4
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), out, 6, 0, 1)
+    idx = np.load(tmp_path / "s1" / "crc32c_index.npy")
+    assert idx.size == 4 and np.all(np.diff(idx) > 0) and idx.max() < 6
+    assert np.array_equal(np.load(tmp_path / "s1" / "crc32c.npy"), crcs[idx.astype(np.int64)].astype(np.float64))
+    for f in ("crc32c.npy", "crc32c_index.npy"):
+        assert np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f))
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_outputs(gpu, tmp_path):
+    """A plain `bench.py --steps K --warmup W` run times exactly K steps and
+    skips everything behind --full; --dump-outputs writes the CRCs of the
+    timed call, equal to the oracle's over the same splitmix blocks."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import wal_oracle as W
+    b = _bench()
+    n, bl = 1027, 4096
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--blocks", str(n), "--no-settle", "--dump-outputs", str(tmp_path / "d")],
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = p.stdout.strip().splitlines()
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["warmup"] == 2 and r["ms_per_step"] > 0 and r["full"] is False
+    assert r["unit"] == "GiB/s" and r["higher_is_better"] is True and r["dtype"] == "u32"
+    assert abs(r["value"] - n * bl / 2**30 / (r["ms_per_step"] * 1e-3)) <= 0.02 * r["value"] + 0.01
+    assert r["roofline"] is None and r["cpu_baseline"] is None and r["c5_strong"] is None
+    got = np.load(tmp_path / "d" / "crc32c.npy")
+    assert got.dtype == np.float64 and got.shape == (n,)
+    L = W.lib()
+    buf = np.empty(n * bl, dtype=np.uint8)
+    L.oracle_fill_splitmix(buf.ctypes.data, 0, buf.size, b.PAYLOAD_SEED)
+    ho = np.arange(n, dtype=np.uint64) * np.uint64(bl)
+    hl = np.full(n, bl, dtype=np.uint32)
+    want = np.zeros(n, dtype=np.uint32)
+    L.oracle_batch(buf.ctypes.data, ho.ctypes.data, hl.ctypes.data, None, want.ctypes.data, n, 0)
+    assert np.array_equal(got, want.astype(np.float64))

@@ -14,8 +14,8 @@ run() {  # tag, then bench args
 }
 for r in 1 2; do
   for w in c2 c4 c3; do
-    run "prod_${w}_$r" --workload $w --api offsets --cpu-seconds 0 --traffic off
-    LVGPU_EXPERIMENT=1 LVGPU_LIB=$var run "var_${w}_$r" --workload $w --api offsets --cpu-seconds 0 --traffic off
+    run "prod_${w}_$r" --workload $w --api offsets --full --cpu-seconds 0 --traffic off
+    LVGPU_EXPERIMENT=1 LVGPU_LIB=$var run "var_${w}_$r" --workload $w --api offsets --full --cpu-seconds 0 --traffic off
   done
   run "prod_table_$r" --table
   LVGPU_EXPERIMENT=1 LVGPU_LIB=$var run "var_table_$r" --table

@@ -20,7 +20,7 @@ mkdir -p "$out"
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$root"
 export TMPDIR=/tmp
-b() { local name=$1; shift; timeout -k 10 400 python3 bench.py "$@" > "$out/$name.json" 2> "$out/$name.err"; }
+b() { local name=$1; shift; timeout -k 10 400 python3 bench.py --full "$@" > "$out/$name.json" 2> "$out/$name.err"; }
 p() { local name=$1; shift
       (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$root/$out/prof_$name" -o "$name" -- \
          python3 "$root/bench.py" --steps 50 --warmup 100 --cpu-seconds 0 --traffic off --c5-strong off "$@") > "$out/prof_$name.log" 2>&1 &&
@@ -51,7 +51,7 @@ p c4 --workload c4 --api offsets &&
 python3 tools/kstats_steady.py "$(ls "$out/prof_wal"/*kernel_trace.csv | head -n 1)" 50 "$out/prof_wal_steady.json" > /dev/null &&
 bash tools/prof_8f.sh "$out/prof8f" table hash wal &&
 bash tools/prof_long.sh "$out/prof_long" &&
-LVGPU_BENCH_BACKEND=gloo timeout -k 10 300 python3 bench.py --gpus 2 --steps 20 --warmup 5 --cpu-seconds 2 > "$out/gloo2.json" 2> "$out/gloo2.err" &&
+LVGPU_BENCH_BACKEND=gloo timeout -k 10 300 python3 bench.py --full --gpus 2 --steps 20 --warmup 5 --cpu-seconds 2 > "$out/gloo2.json" 2> "$out/gloo2.err" &&
 for d in "$out"/prof_*/; do find "$d" -name '*kernel_trace.csv' -size +1M -delete; done; }
 case $part in
   bench) bench_part ;;
