@@ -12,7 +12,10 @@
  *
  * Writer side (log_writer.rs): many logical records are laid out exactly as
  * Writer::add_record does (log_writer.rs:62-110) and every fragment header's
- * masked CRC (log_writer.rs:123-125) comes from one GPU batch.
+ * masked CRC (log_writer.rs:123-125) comes from one GPU batch.  From host
+ * memory (lv_wal_encode_host) the bytes are laid out by host threads; with the
+ * payload already in HBM (lv_wal_encode_device) the log is written there too,
+ * by a kernel that produces it in aligned 16-byte stores.
  */
 #ifndef LVGPU_WAL_H
 #define LVGPU_WAL_H
@@ -106,6 +109,48 @@ void lv_wal_reader_free(lv_wal_reader *reader);
  * small, only *out_len is set and LV_ERR_INVALID is returned. */
 int lv_wal_encode_host(const uint8_t *payload, const uint64_t *rec_off, const uint64_t *rec_len, size_t n,
                        uint64_t dest_length, uint8_t *out, size_t out_cap, size_t *out_len, int device);
+
+/* Host, pure, no GPU: the number of bytes Writer::add_record appends for n
+ * records of these lengths to a log whose Writer has already written
+ * dest_length bytes (log_writer.rs:48-56; only dest_length % 32768 matters).
+ * *fragments (may be NULL) = physical records emitted. */
+size_t lv_wal_encode_size(const uint64_t *rec_len, size_t n, uint64_t dest_length, size_t *fragments);
+
+/* Device workspace of lv_wal_encode_device for a batch of `fragments` physical
+ * records: the fragment table and its CRCs (32 bytes per fragment) plus
+ * lv_crc32c_workspace_bytes(fragments). */
+size_t lv_wal_encode_workspace_bytes(size_t fragments);
+
+/* lv_wal_encode_host with the payload and the output in device memory.
+ * rec_off / rec_len are HOST arrays (the group-commit writer knows its
+ * records' lengths on the host, as lv_batch_hint already assumes); record i is
+ * d_payload[rec_off[i] .. rec_off[i]+rec_len[i]).  Records may overlap, repeat
+ * or be in any order within d_payload[0, payload_bytes).  Writes exactly
+ * d_out[0, *out_len) and no other byte; *out_len is always set; if d_out is
+ * NULL or out_cap is too small, LV_ERR_INVALID and nothing is enqueued (a
+ * batch that appends no bytes -- n == 0 -- is LV_OK with nothing enqueued).
+ * Stream-ordered and asynchronous; the host arrays are consumed before return.
+ *
+ * d_payload and d_out may have any byte alignment; d_out[0, *out_len) must not
+ * overlap d_payload[0, payload_bytes).  d_workspace: at least
+ * lv_wal_encode_workspace_bytes(fragments) bytes, 16-B aligned, not shared
+ * with a call that may run concurrently.  Every argument is checked on the
+ * host before any device call (LV_ERR_INVALID, lv_last_error).
+ *
+ * Limit: a batch may emit at most 2^32-1 fragments, what one
+ * lv_crc32c_batch_device call accepts; more is LV_ERR_INVALID.
+ *
+ * Two steps on `stream`, no host synchronisation: the fragment table goes up
+ * through page-locked staging the library owns (a staging buffer is reused
+ * only after the copy that read it has completed, so calls enqueued back to
+ * back, on one stream or several, never share one) and the offsets API
+ * checksums every fragment where it lies in d_payload; then wal_frame_kernel
+ * writes the log, every 16-byte granule of d_out with one aligned store.  The
+ * call asks the runtime whether earlier copies have finished, which a stream
+ * capture does not allow: do not capture it into a HIP graph. */
+int lv_wal_encode_device(const uint8_t *d_payload, uint64_t payload_bytes, const uint64_t *rec_off,
+                         const uint64_t *rec_len, size_t n, uint64_t dest_length, uint8_t *d_out, size_t out_cap,
+                         size_t *out_len, void *d_workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace lvgpu_internal {
@@ -52,6 +53,27 @@ struct lv_wal_scan {
 };
 
 namespace lvgpu_internal {
+// Writer::add_record's layout of n records (wal_layout.cc, host only).
+struct WalFrag {
+    uint64_t out_pos;  // header position in the appended bytes
+    uint64_t src;      // payload source offset
+    uint32_t len;
+    uint8_t type;
+};
+struct WalLayout {
+    std::vector<WalFrag> frags;                       // ascending out_pos; never straddle a block
+    std::vector<std::pair<uint64_t, uint64_t>> pads;  // (out_pos, bytes) of zero trailers
+    // first fragment of each 32 KiB block of the appended span, plus the
+    // fragment count at the end (empty when there are no records)
+    std::vector<uint64_t> block_first;
+    uint64_t out_len = 0;    // bytes appended
+    uint64_t fragments = 0;  // physical records emitted
+};
+// rec_off may be null (sources 0).  table = false fills only out_len and
+// fragments.
+void wal_layout(const uint64_t *rec_off, const uint64_t *rec_len, size_t n, uint64_t dest_length, bool table,
+                WalLayout *out);
+
 int set_error(int code, const char *msg);  // lv_last_error plumbing (context.hip)
 void clear_error();
 int launch_status();                       // hipGetLastError -> LV status + message

@@ -349,43 +349,14 @@ void lv_wal_reader_free(lv_wal_reader *reader) { delete reader; }
 int lv_wal_encode_host(const uint8_t *payload, const uint64_t *rec_off, const uint64_t *rec_len, size_t n,
                        uint64_t dest_length, uint8_t *out, size_t out_cap, size_t *out_len, int device) {
     if (!out_len || (n && (!rec_off || !rec_len))) return lvgpu_internal::set_error(LV_ERR_INVALID, "null argument");
-    // Pass 1: layout (log_writer.rs:62-110), identical block arithmetic.
-    struct Frag {
-        uint64_t out_pos;   // header position in `out`
-        uint64_t src;       // payload source offset
-        uint32_t len;
-        uint8_t type;
-    };
-    std::vector<Frag> frags;
-    std::vector<std::pair<uint64_t, uint64_t>> pads;  // (out_pos, bytes) of zero trailers
-    uint64_t block_offset = dest_length % kBlock;     // log_writer.rs:48-56
-    uint64_t pos = 0;
-    for (size_t r = 0; r < n; ++r) {
-        uint64_t left = rec_len[r];
-        uint64_t src = rec_off[r];
-        bool begin = true;
-        for (;;) {
-            const uint64_t leftover = kBlock - block_offset;
-            if (leftover < kHeader) {
-                if (leftover > 0) {
-                    pads.emplace_back(pos, leftover);
-                    pos += leftover;
-                }
-                block_offset = 0;
-            }
-            const uint64_t avail = kBlock - block_offset - kHeader;
-            const uint64_t frag_len = left < avail ? left : avail;
-            const bool end = left == frag_len;
-            const uint8_t type = begin && end ? kFull : begin ? kFirst : end ? kLast : kMiddle;
-            frags.push_back({pos, src, static_cast<uint32_t>(frag_len), type});
-            pos += kHeader + frag_len;
-            block_offset += kHeader + frag_len;
-            src += frag_len;
-            left -= frag_len;
-            begin = false;
-            if (left == 0) break;
-        }
-    }
+    // Pass 1: layout (log_writer.rs:62-110), identical block arithmetic
+    // (wal_layout.cc, shared with the device encoder).
+    using Frag = lvgpu_internal::WalFrag;
+    lvgpu_internal::WalLayout lay;
+    lvgpu_internal::wal_layout(rec_off, rec_len, n, dest_length, true, &lay);
+    const std::vector<Frag> &frags = lay.frags;
+    const auto &pads = lay.pads;
+    const uint64_t pos = lay.out_len;
     *out_len = pos;
     if (!out || out_cap < pos) return lvgpu_internal::set_error(LV_ERR_INVALID, "output buffer too small");
     // Pass 2: the fragment CRCs and the bytes, concurrently.  A fragment's CRC

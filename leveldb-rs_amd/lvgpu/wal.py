@@ -7,6 +7,10 @@
                                       (log_reader.rs:75-120, :99)
     encode(records, dest_length)      Writer::add_record over many records with one
                                       GPU batch for the header CRCs (log_writer.rs:62-134)
+    encode_size(rec_len, dest_length) bytes and fragments of that layout (host, no GPU)
+    encode_device(payload_tensor, rec_off, rec_len, dest_length)
+                                      the same log written in HBM from a payload in HBM:
+                                      fragment CRCs + wal_frame_kernel, no host sync
 """
 from __future__ import annotations
 
@@ -59,6 +63,12 @@ def _bind():
     L.lv_wal_scan_device.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, sz, vp]
     L.lv_wal_encode_host.restype = ctypes.c_int
     L.lv_wal_encode_host.argtypes = [vp, vp, vp, sz, u64, vp, sz, ctypes.POINTER(ctypes.c_size_t), ctypes.c_int]
+    L.lv_wal_encode_size.restype = sz
+    L.lv_wal_encode_size.argtypes = [vp, sz, u64, ctypes.POINTER(ctypes.c_size_t)]
+    L.lv_wal_encode_workspace_bytes.restype = sz
+    L.lv_wal_encode_workspace_bytes.argtypes = [sz]
+    L.lv_wal_encode_device.restype = ctypes.c_int
+    L.lv_wal_encode_device.argtypes = [vp, u64, vp, vp, sz, u64, vp, sz, ctypes.POINTER(ctypes.c_size_t), vp, sz, vp]
     _bound = True
     return L
 
@@ -231,3 +241,52 @@ def encode(records, dest_length: int = 0, device: int = 0) -> bytes:
     if rc != 0:
         _err("lv_wal_encode_host")
     return out.raw[: need.value]
+
+
+def encode_size(rec_len, dest_length: int = 0):
+    """(bytes, fragments) Writer::add_record appends for records of these
+    lengths to a log of dest_length bytes (lv_wal_encode_size; host, no GPU)."""
+    L = _bind()
+    ln = np.ascontiguousarray(rec_len, dtype=np.uint64)
+    frags = ctypes.c_size_t()
+    nbytes = L.lv_wal_encode_size(ln.ctypes.data, ln.size, dest_length, ctypes.byref(frags))
+    return int(nbytes), int(frags.value)
+
+
+def encode_workspace_bytes(fragments: int) -> int:
+    return int(_bind().lv_wal_encode_workspace_bytes(fragments))
+
+
+def encode_device(payload, rec_off, rec_len, dest_length: int = 0, out=None, workspace=None, stream=None):
+    """lv_wal_encode_device: the bytes Writer::add_record appends for the
+    records payload[rec_off[i] : rec_off[i] + rec_len[i]] (host arrays; any
+    order, overlaps allowed), written in HBM.  `payload` is a uint8 CUDA tensor;
+    returns a uint8 CUDA tensor view of exactly the appended bytes (of `out` if
+    given: a uint8 tensor on the payload's device, at least encode_size bytes).
+    Asynchronous on `stream`."""
+    import torch
+    from . import _dev_ptr, _stream_ptr
+    L = _bind()
+    if payload.dtype != torch.uint8:
+        raise LvError(f"payload must be a uint8 tensor (got {payload.dtype}: numel() would not count bytes)")
+    dev = payload.device
+    for name, t in (("out", out), ("workspace", workspace)):
+        if t is not None and (t.dtype != torch.uint8 or t.device != dev):
+            raise LvError(f"{name} must be a uint8 tensor on the payload's device")
+    off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+    ln = np.ascontiguousarray(rec_len, dtype=np.uint64)
+    if off.size != ln.size:
+        raise LvError("rec_off/rec_len size mismatch")
+    nbytes, frags = encode_size(ln, dest_length)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(L.lv_wal_encode_workspace_bytes(frags), dtype=torch.uint8, device=dev)
+    got = ctypes.c_size_t()
+    with torch.cuda.device(dev):  # the C call runs on the current device
+        rc = L.lv_wal_encode_device(_dev_ptr(payload, "payload"), payload.numel(), off.ctypes.data, ln.ctypes.data,
+                                    ln.size, dest_length, _dev_ptr(out, "out"), out.numel(), ctypes.byref(got),
+                                    _dev_ptr(workspace, "workspace"), workspace.numel(), _stream_ptr(stream))
+    if rc != 0:
+        _err("lv_wal_encode_device")
+    return out[: got.value]
