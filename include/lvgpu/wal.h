@@ -152,6 +152,94 @@ int lv_wal_encode_device(const uint8_t *d_payload, uint64_t payload_bytes, const
                          const uint64_t *rec_len, size_t n, uint64_t dest_length, uint8_t *d_out, size_t out_cap,
                          size_t *out_len, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Device-resident Reader: the inverse of lv_wal_encode_device ----------
+ *
+ * lv_wal_decode_device replays Reader::read_record (log_reader.rs:120-364, as
+ * lv_wal_reader restates it) over a log in HBM and the arrays
+ * lv_wal_scan_device made of the same d_log and bytes: stored checksums are
+ * compared with the computed ones, FIRST/MIDDLE/LAST fragments are joined into
+ * logical records, and the Reader's drop rules are applied and reported.
+ * Scope: Reader::new(.., initial_offset = 0).  An initial offset and the
+ * resyncing it brings are not offered; use lv_wal_reader for those.
+ * As in lv_wal_reader and the reference, a well-formed physical record whose
+ * type byte is 5 or 6 reads as the Reader's own Eof / BadRecord code: type 5
+ * ends the replay there, silently (nothing after it is read or reported), and
+ * type 6 drops an open record ("error in middle of record") and reading goes
+ * on; types >= 7 are "unknown record type".
+ *
+ * Output (all device memory the caller owns): record r is
+ * d_payload[d_rec_off[r], d_rec_off[r] + d_rec_len[r]) -- the records lie end
+ * to end in log order, d_rec_off[0] = 0 -- and d_rec_log_off[r] is what
+ * Reader::last_record_offset returns after reading it (the header offset of
+ * its FULL or FIRST fragment).  Report q is what Reporter::corruption received
+ * q-th: d_rep_bytes[q] bytes for d_rep_reason[q] (LV_WAL_DROP_*), and
+ * d_rep_log_off[q] is the header offset of the physical record at which the
+ * Reader made it.  *d_totals is always written: the numbers of records,
+ * payload bytes and reports, the sum of the reports' byte counts, and status.
+ *
+ * Capacities.  rec_cap = scan_cap, rep_cap = 2 * scan_cap and payload_cap =
+ * bytes always suffice, so everything can be sized without a round trip:
+ * every record ends at a scan entry of its own (its FULL or LAST), an entry
+ * makes at most two reports (a kill inside an open record: the kill, then
+ * "error in middle of record"), and every payload byte is a log byte.  If a
+ * capacity is exceeded, or the scan itself overflowed (*d_count > scan_cap:
+ * it wrote no entries, and the totals are those of an empty log), only
+ * *d_totals is written, with the true totals and the LV_WAL_DECODE_*_OVER
+ * bits; otherwise status == 0.  d_rep_bytes / d_rep_log_off / d_rep_reason
+ * may all be NULL with rep_cap == 0: reports are then only counted and
+ * REPORT_OVER is not raised.
+ *
+ * Arguments.  d_hdr_off / d_crc / d_info / d_count are exactly what
+ * lv_wal_scan_device wrote for d_log[0, bytes) at capacity scan_cap (read in
+ * stream order; *d_count is read on the device, never on the host).  d_log is
+ * 8-B aligned, d_payload may have any byte alignment, and
+ * d_payload[0, payload_cap) must not overlap d_log[0, bytes).  d_workspace:
+ * >= lv_wal_decode_workspace_bytes(scan_cap) bytes, 16-B aligned, not shared
+ * with a call that may run concurrently.  Every argument is checked on the
+ * host before any device call (LV_ERR_INVALID, lv_last_error).
+ *
+ * Stream-ordered, no host synchronisation: one memset and five launches on
+ * `stream`, sized by scan_cap (threads beyond *d_count do nothing).  Unlike
+ * lv_wal_encode_device the call stages nothing and asks the runtime nothing
+ * about the stream's progress, so it may be captured into a HIP graph, once
+ * the device has been initialised (lv_device_init or any earlier call). */
+#define LV_WAL_DECODE_NO_CHECKSUM 0x1u   /* Reader::new(checksum = false): d_crc may be NULL */
+
+/* reasons, one per string lv_wal_reader reports with initial_offset == 0 */
+#define LV_WAL_DROP_BAD_LENGTH 1u        /* "bad record length" */
+#define LV_WAL_DROP_CHECKSUM 2u          /* "checksum mismatch" */
+#define LV_WAL_DROP_MID_RECORD 3u        /* "error in middle of record" */
+#define LV_WAL_DROP_NO_END_1 4u          /* "partial record without end(1)" */
+#define LV_WAL_DROP_NO_END_2 5u          /* "partial record without end(2)" */
+#define LV_WAL_DROP_NO_START_1 6u        /* "missing start of fragmented record(1)" */
+#define LV_WAL_DROP_NO_START_2 7u        /* "missing start of fragmented record(2)" */
+#define LV_WAL_DROP_UNEXPECTED_TYPE 8u   /* "unexpected record type" */
+#define LV_WAL_DROP_UNKNOWN_TYPE 9u      /* "unknown record type" */
+
+/* status bits in lv_wal_decode_totals.status */
+#define LV_WAL_DECODE_SCAN_OVER 1u       /* *d_count > scan_cap: the scan itself wrote nothing */
+#define LV_WAL_DECODE_REC_OVER 2u
+#define LV_WAL_DECODE_PAYLOAD_OVER 4u
+#define LV_WAL_DECODE_REPORT_OVER 8u
+
+typedef struct lv_wal_decode_totals {   /* device memory, 8-B aligned, always written */
+    uint64_t records, payload_bytes, reports, dropped_bytes, status;
+} lv_wal_decode_totals;
+
+typedef struct lv_wal_decode_out {      /* every pointer is device memory the caller owns */
+    uint8_t *d_payload;   size_t payload_cap;   /* any byte alignment */
+    uint64_t *d_rec_off, *d_rec_len, *d_rec_log_off;  size_t rec_cap;
+    uint64_t *d_rep_bytes, *d_rep_log_off;  uint32_t *d_rep_reason;  size_t rep_cap;
+    lv_wal_decode_totals *d_totals;
+} lv_wal_decode_out;
+
+size_t lv_wal_decode_workspace_bytes(size_t scan_cap);
+int lv_wal_decode_device(const uint8_t *d_log, size_t bytes,
+                         const uint64_t *d_hdr_off, const uint32_t *d_crc, const uint32_t *d_info,
+                         const uint64_t *d_count, size_t scan_cap,
+                         const lv_wal_decode_out *out, uint32_t flags,
+                         void *d_workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,13 @@
     encode_device(payload_tensor, rec_off, rec_len, dest_length)
                                       the same log written in HBM from a payload in HBM:
                                       fragment CRCs + wal_frame_kernel, no host sync
+    decode_device(log_tensor, hdr_off, crc, info, count)
+                                      the inverse: Reader::read_record (initial_offset 0)
+                                      replayed in HBM over scan_device's arrays -- records
+                                      packed end to end, their offsets / lengths /
+                                      last_record_offset, the corruption reports in order,
+                                      totals; no host sync until .records() / .reports()
+    decode_workspace_bytes(scan_cap)  device workspace of decode_device
 """
 from __future__ import annotations
 
@@ -23,6 +30,34 @@ from . import LvError, lib
 BLOCK_SIZE = 32768
 HEADER_SIZE = 7
 REC_OK, REC_BAD_LENGTH, REC_ZERO = 0, 1, 2
+
+DECODE_NO_CHECKSUM = 0x1  # LV_WAL_DECODE_NO_CHECKSUM
+# LV_WAL_DROP_*: the strings lv_wal_reader reports (log_reader.rs:120-364)
+DROP_REASONS = {
+    1: "bad record length",
+    2: "checksum mismatch",
+    3: "error in middle of record",
+    4: "partial record without end(1)",
+    5: "partial record without end(2)",
+    6: "missing start of fragmented record(1)",
+    7: "missing start of fragmented record(2)",
+    8: "unexpected record type",
+    9: "unknown record type",
+}
+# LV_WAL_DECODE_*_OVER
+DECODE_STATUS = {1: "SCAN_OVER", 2: "REC_OVER", 4: "PAYLOAD_OVER", 8: "REPORT_OVER"}
+DECODE_TILE = 1024  # entries per tile of the decode's scan (kDecTile, csrc/wal_decode.hip)
+
+
+class DecodeOut(ctypes.Structure):
+    """lv_wal_decode_out (include/lvgpu/wal.h)."""
+    _fields_ = [("d_payload", ctypes.c_void_p), ("payload_cap", ctypes.c_size_t),
+                ("d_rec_off", ctypes.c_void_p), ("d_rec_len", ctypes.c_void_p), ("d_rec_log_off", ctypes.c_void_p),
+                ("rec_cap", ctypes.c_size_t),
+                ("d_rep_bytes", ctypes.c_void_p), ("d_rep_log_off", ctypes.c_void_p), ("d_rep_reason", ctypes.c_void_p),
+                ("rep_cap", ctypes.c_size_t),
+                ("d_totals", ctypes.c_void_p)]
+
 
 _REPORTER = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p)
 _bound = False
@@ -69,6 +104,11 @@ def _bind():
     L.lv_wal_encode_workspace_bytes.argtypes = [sz]
     L.lv_wal_encode_device.restype = ctypes.c_int
     L.lv_wal_encode_device.argtypes = [vp, u64, vp, vp, sz, u64, vp, sz, ctypes.POINTER(ctypes.c_size_t), vp, sz, vp]
+    L.lv_wal_decode_workspace_bytes.restype = sz
+    L.lv_wal_decode_workspace_bytes.argtypes = [sz]
+    L.lv_wal_decode_device.restype = ctypes.c_int
+    L.lv_wal_decode_device.argtypes = [vp, sz, vp, vp, vp, vp, sz, ctypes.POINTER(DecodeOut), ctypes.c_uint32, vp, sz,
+                                       vp]
     _bound = True
     return L
 
@@ -290,3 +330,123 @@ def encode_device(payload, rec_off, rec_len, dest_length: int = 0, out=None, wor
     if rc != 0:
         _err("lv_wal_encode_device")
     return out[: got.value]
+
+
+def decode_workspace_bytes(scan_cap: int) -> int:
+    return int(_bind().lv_wal_decode_workspace_bytes(scan_cap))
+
+
+class Decoded:
+    """Outputs of decode_device, all CUDA tensors written asynchronously:
+    payload (uint8), rec_off / rec_len / rec_log_off (int64), rep_bytes /
+    rep_log_off (int64) and rep_reason (int32) -- None when reports are only
+    counted -- and totals (int64[5]: records, payload_bytes, reports,
+    dropped_bytes, status)."""
+
+    def __init__(self, payload, rec_off, rec_len, rec_log_off, rep_bytes, rep_log_off, rep_reason, totals, keep):
+        self.payload, self.rec_off, self.rec_len, self.rec_log_off = payload, rec_off, rec_len, rec_log_off
+        self.rep_bytes, self.rep_log_off, self.rep_reason, self.totals = rep_bytes, rep_log_off, rep_reason, totals
+        self._keep = keep  # the inputs and the workspace, until the work has run
+        self._tot = None
+
+    def sync_totals(self) -> dict:
+        """Waits for the decode; the totals as a dict.  Raises LvError naming
+        the status bits if a capacity was exceeded (nothing else was written)."""
+        if self._tot is None:
+            import torch
+            torch.cuda.synchronize(self.totals.device)
+            t = [int(v) for v in self.totals.cpu().numpy().view(np.uint64)]
+            self._tot = dict(zip(("records", "payload_bytes", "reports", "dropped_bytes", "status"), t))
+            self._keep = None
+        st = self._tot["status"]
+        if st:
+            names = "|".join(n for b, n in DECODE_STATUS.items() if st & b)
+            raise LvError(f"lv_wal_decode_device: status {names} (totals {self._tot})")
+        return self._tot
+
+    def records(self):
+        """The logical records, list[bytes] (synchronises)."""
+        t = self.sync_totals()
+        n = t["records"]
+        pay = self.payload[: t["payload_bytes"]].cpu().numpy().tobytes()
+        off = self.rec_off[:n].cpu().numpy()
+        ln = self.rec_len[:n].cpu().numpy()
+        return [pay[int(o):int(o + k)] for o, k in zip(off, ln)]
+
+    def record_log_offsets(self):
+        """Reader::last_record_offset after each record (synchronises)."""
+        return [int(v) for v in self.rec_log_off[: self.sync_totals()["records"]].cpu().numpy()]
+
+    def reports(self):
+        """[(bytes, reason string)] in the Reader's order (synchronises)."""
+        t = self.sync_totals()
+        if self.rep_bytes is None:
+            raise LvError("decode_device ran with reports=False: they were only counted")
+        n = t["reports"]
+        b = self.rep_bytes[:n].cpu().numpy()
+        r = self.rep_reason[:n].cpu().numpy()
+        return [(int(x), DROP_REASONS[int(y)]) for x, y in zip(b, r)]
+
+
+def decode_device(log, hdr_off, crc, info, count, *, checksum: bool = True, payload=None, workspace=None,
+                  stream=None, reports: bool = True, rec_cap=None, rep_cap=None, scan_cap=None, fill=None):
+    """lv_wal_decode_device over the tensors scan_device returned for `log` (a
+    uint8 CUDA tensor, 8-B aligned): Reader::read_record with initial_offset 0,
+    replayed in HBM.  Returns a Decoded; asynchronous on `stream`.  `payload`
+    (uint8, any alignment, not overlapping the log) defaults to log.numel()
+    bytes; rec_cap / rep_cap default to scan_cap / 2 * scan_cap, which always
+    suffice.  checksum=False is LV_WAL_DECODE_NO_CHECKSUM (crc may be None);
+    reports=False passes NULL report arrays: reports are only counted.
+    scan_cap is the capacity scan_device ran with (default hdr_off.numel(),
+    right for any cap >= 1); fill, a byte value, initialises the record and
+    report arrays with it first (canaries)."""
+    import torch
+    from . import _dev_ptr, _stream_ptr
+    L = _bind()
+    if log.dtype != torch.uint8:
+        raise LvError(f"log must be a uint8 tensor (got {log.dtype}: numel() would not count bytes)")
+    dev = log.device
+    for name, t, dt in (("hdr_off", hdr_off, torch.int64), ("crc", crc, torch.int32), ("info", info, torch.int32),
+                        ("count", count, torch.int64), ("payload", payload, torch.uint8),
+                        ("workspace", workspace, torch.uint8)):
+        if t is None and (name in ("payload", "workspace") or (name == "crc" and not checksum)):
+            continue
+        if t is None or t.dtype != dt or t.device != dev:
+            raise LvError(f"{name} must be a {dt} tensor on the log's device")
+    scan_cap = int(hdr_off.numel()) if scan_cap is None else int(scan_cap)
+    if hdr_off.numel() < scan_cap or info.numel() < scan_cap or (crc is not None and crc.numel() < scan_cap) or count.numel() < 1:
+        raise LvError("crc / info must hold hdr_off.numel() entries and count one")
+    rec_cap = scan_cap if rec_cap is None else int(rec_cap)
+    rep_cap = (2 * scan_cap if rep_cap is None else int(rep_cap)) if reports else 0
+    if payload is None:
+        payload = torch.empty(log.numel(), dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(L.lv_wal_decode_workspace_bytes(scan_cap), dtype=torch.uint8, device=dev)
+    def alloc(n, dt):
+        if fill is None:
+            return torch.empty(max(n, 1), dtype=dt, device=dev)
+        width = torch.empty(0, dtype=dt).element_size()
+        return torch.full((max(n, 1) * width,), fill, dtype=torch.uint8, device=dev).view(dt)
+    i64 = lambda n: alloc(n, torch.int64)
+    rec_off, rec_len, rec_log = i64(rec_cap), i64(rec_cap), i64(rec_cap)
+    rep_bytes = rep_log = rep_reason = None
+    if reports:
+        rep_bytes, rep_log = i64(rep_cap), i64(rep_cap)
+        rep_reason = alloc(rep_cap, torch.int32)
+    totals = torch.empty(5, dtype=torch.int64, device=dev)
+    o = DecodeOut()
+    o.d_payload, o.payload_cap = _dev_ptr(payload, "payload"), payload.numel()
+    o.d_rec_off, o.d_rec_len, o.d_rec_log_off = (_dev_ptr(t, "rec") for t in (rec_off, rec_len, rec_log))
+    o.rec_cap = rec_cap
+    o.d_rep_bytes, o.d_rep_log_off, o.d_rep_reason = (_dev_ptr(t, "rep") for t in (rep_bytes, rep_log, rep_reason))
+    o.rep_cap = rep_cap
+    o.d_totals = _dev_ptr(totals, "totals")
+    with torch.cuda.device(dev):  # the C call runs on the current device
+        rc = L.lv_wal_decode_device(_dev_ptr(log, "log"), log.numel(), _dev_ptr(hdr_off, "hdr_off"),
+                                    _dev_ptr(crc, "crc"), _dev_ptr(info, "info"), _dev_ptr(count, "count"), scan_cap,
+                                    ctypes.byref(o), 0 if checksum else DECODE_NO_CHECKSUM,
+                                    _dev_ptr(workspace, "workspace"), workspace.numel(), _stream_ptr(stream))
+    if rc != 0:
+        _err("lv_wal_decode_device")
+    return Decoded(payload, rec_off, rec_len, rec_log, rep_bytes, rep_log, rep_reason, totals,
+                   (log, hdr_off, crc, info, count, workspace))
