@@ -1,0 +1,615 @@
+// lv_write_batch_decode_device: WriteBatch::iterate (write_batch.rs:92-122)
+// over the logical records lv_wal_decode_device left in HBM, to a flat,
+// log-ordered op table.  The format is sequential inside a record and
+// independent across records, so the call is three stages:
+//
+//   wb_count   every record is walked once: its emitted op count and status,
+//              the sums for the totals, each tile's op count.
+//   wb_tiles   (one workgroup) the exclusive scan of the tile counts, the
+//              totals and the status.
+//   wb_emit    every record with ops is walked again and its ops are written
+//              at its base (tile base + the scan inside the tile).
+//
+// Count and emit share one walk (wb_walk), templated on the byte source and on
+// what is done with an op.  Two record classes use it, chosen per record on
+// the device by d_rec_len:
+//
+//   small (<= kWbSmall bytes): one lane per record.  Neighbouring lanes own
+//   neighbouring records, which lie next to each other in d_payload; a lane
+//   reads the aligned 16-B granule under the byte it needs into registers.
+//
+//   large: one wave per record, through an LDS window of kWbWindow bytes the
+//   wave loads with coalesced 16-B loads.  The walk runs wave-uniformly over
+//   the window (all lanes read the same LDS address: a broadcast); lane k % 64
+//   keeps op k in registers and every 64 ops the wave stores them together.
+//   When the parser needs a byte outside the window, the next window starts at
+//   that byte's granule: keys and values are skipped, not read.
+//
+// A wave takes 64 consecutive records at a time: each lane walks its own if it
+// is small, then the wave walks the large ones among them one after another.
+// All position arithmetic is u64.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "../../include/lvgpu/crc32c.h"
+#include "../../include/lvgpu/write_batch.h"
+#include "lv_internal.h"
+#include "lvh.h"
+
+namespace lvk {
+
+constexpr uint32_t kWbThreads = 256;
+constexpr uint32_t kWbPer = 1;                        // records per thread of a scan tile
+constexpr uint32_t kWbTile = kWbThreads * kWbPer;     // records per scan tile
+constexpr uint32_t kWbWaves = kWbThreads / 64;
+constexpr uint32_t kWbChunks = kWbTile / 64;          // 64-record chunks of a tile
+constexpr uint32_t kWbSmall = 16384;                  // records up to this many bytes: one lane each
+constexpr uint32_t kWbWindow = 4096;                  // LDS window of a wave-class record, bytes
+constexpr uint32_t kWbRound = 64 * 16;                // one load of the wave: 64 lanes x 16 B
+constexpr uint32_t kWbWinPad = 16;                    // LDS behind a window: the 12-byte register refill may run into it
+constexpr uint32_t kWbScanThreads = 1024;             // wb_tiles' one workgroup
+static_assert(kWbWindow % kWbRound == 0 && kWbWindow > kWbRound, "a window is whole rounds, more than one");
+static_assert(kWbSmall >= LV_WB_HEADER_SIZE, "the lane class takes whole headers");
+
+typedef uint32_t wb_u4 __attribute__((ext_vector_type(4)));
+
+// What the count pass keeps of the whole batch (workspace, zeroed by the
+// call's memset), and what wb_tiles adds for wb_emit.
+struct WbHead {
+    unsigned long long key_bytes, val_bytes, bad, last_seq;
+    uint64_t n, status, pad[2];
+};
+
+struct WbArgs {
+    const uint8_t *payload;
+    uint64_t payload_bytes;
+    const uint64_t *rec_off, *rec_len, *records, *upstream;
+    uint64_t rec_cap;
+    lv_wb_decode_out out;
+    // workspace
+    WbHead *head;
+    uint64_t *cnt;     // ops of each record
+    uint32_t *st;      // status of each record
+    uint64_t *tsum;    // ops of each tile, then (wb_tiles) the ops before it
+};
+
+// Records to walk: none when upstream wrote no arrays or the arrays are too
+// short for what it counted.
+__device__ __forceinline__ uint64_t wb_records(const WbArgs &A) {
+    if (A.upstream && *A.upstream) return 0;
+    const uint64_t n = *A.records;
+    return n > A.rec_cap ? 0ull : n;
+}
+
+// ---- byte sources ---------------------------------------------------------
+// One lane: the aligned granule under the last byte asked for, in registers.
+struct WbLaneSrc {
+    const uint8_t *p;
+    uint64_t gi;
+    wb_u4 g;
+    __device__ __forceinline__ explicit WbLaneSrc(const uint8_t *payload) : p(payload), gi(~0ull), g{0, 0, 0, 0} {}
+    __device__ __forceinline__ uint32_t byte(uint64_t a) {
+        const uint64_t addr = reinterpret_cast<uint64_t>(p) + a;
+        const uint64_t q = addr >> 4;
+        if (q != gi) {
+            g = *reinterpret_cast<const wb_u4 *>(q << 4);
+            gi = q;
+        }
+        const uint32_t i = static_cast<uint32_t>(addr) & 15u;
+        const uint32_t w = i < 8 ? (i < 4 ? g.x : g.y) : (i < 12 ? g.z : g.w);
+        return (w >> (8 * (i & 3u))) & 0xffu;
+    }
+};
+
+// One wave: a window of kWbWindow bytes in LDS, from an aligned address.  A
+// window opens where the parser lands after a skip, with its first round
+// (kWbRound bytes: an entry's header after a long value is all that is wanted
+// of it); when the walk runs on past that round, the rest of the window is
+// loaded at once.  Only granules that begin before the record's end are loaded
+// (the rest read as 0 and are never asked for), so nothing is read past the
+// granule that holds the record's last byte.  Every call is wave-uniform.
+struct WbWaveSrc {
+    const uint8_t *p;
+    uint8_t *lds;
+    uint64_t lo, end;  // window start address (16-B aligned; ~0: none), record end address
+    uint32_t have;     // bytes of the window that are loaded
+    uint32_t lane;
+    // the rn (<= 8) bytes from address ra on, in a register pair: an entry's
+    // header is parsed from it, so the LDS round trip is paid once per header,
+    // not once per byte
+    uint64_t ra, rw;
+    uint32_t rn;
+    __device__ __forceinline__ WbWaveSrc(const uint8_t *payload, uint8_t *window, uint64_t rec_end, uint32_t l)
+        : p(payload), lds(window), lo(~0ull), end(reinterpret_cast<uint64_t>(payload) + rec_end), have(0), lane(l),
+          ra(0), rw(0), rn(0) {}
+    __device__ __forceinline__ void load(uint32_t from, uint32_t to) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();  // the reads of the old window are done
+        for (uint32_t slot = from / 16 + lane; slot < to / 16; slot += 64) {
+            const uint64_t ga = lo + static_cast<uint64_t>(slot) * 16;
+            wb_u4 v{0, 0, 0, 0};
+            if (ga < end) v = *reinterpret_cast<const wb_u4 *>(ga);
+            reinterpret_cast<wb_u4 *>(lds)[slot] = v;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    __device__ __forceinline__ void refill(uint64_t addr) {
+        if (lo == ~0ull || addr < lo || addr - lo >= kWbWindow) {
+            lo = addr & ~15ull;
+            have = 0;
+        }
+        const uint32_t at = static_cast<uint32_t>(addr - lo);
+        if (at >= have) {  // a new window: its first round; running on: the rest
+            const uint32_t to = have ? kWbWindow : kWbRound;
+            load(have, to);
+            have = to;
+        }
+        // 8 bytes from `at`: three aligned words and a byte shift (the last
+        // may lie in the pad behind the window; only rn bytes are ever used)
+        const uint32_t *w = reinterpret_cast<const uint32_t *>(lds + (at & ~3u));
+        const uint32_t d0 = w[0], d1 = w[1], d2 = w[2], s = at & 3u;
+        const uint32_t l32 = __builtin_amdgcn_alignbyte(d1, d0, s), h32 = __builtin_amdgcn_alignbyte(d2, d1, s);
+        rw = (static_cast<uint64_t>(h32) << 32) | l32;
+        ra = addr;
+        rn = have - at < 8u ? have - at : 8u;
+    }
+    __device__ __forceinline__ uint32_t byte(uint64_t a) {
+        const uint64_t addr = reinterpret_cast<uint64_t>(p) + a;
+        uint64_t d = addr - ra;
+        if (d >= rn) {
+            refill(addr);
+            d = 0;
+        }
+        return static_cast<uint32_t>(rw >> (8u * static_cast<uint32_t>(d))) & 0xffu;
+    }
+};
+
+// ---- op sinks -------------------------------------------------------------
+struct WbNoSink {
+    __device__ __forceinline__ void put(uint64_t, uint64_t, uint64_t, uint64_t, uint32_t, uint32_t) {}
+    __device__ __forceinline__ void finish(uint64_t) {}
+};
+
+__device__ __forceinline__ void wb_store_op(lv_wb_op *dst, uint64_t tag, uint64_t koff, uint64_t voff, uint32_t klen,
+                                            uint32_t vlen) {
+    wb_u4 a, b;
+    a.x = static_cast<uint32_t>(tag);
+    a.y = static_cast<uint32_t>(tag >> 32);
+    a.z = static_cast<uint32_t>(koff);
+    a.w = static_cast<uint32_t>(koff >> 32);
+    b.x = static_cast<uint32_t>(voff);
+    b.y = static_cast<uint32_t>(voff >> 32);
+    b.z = klen;
+    b.w = vlen;
+    wb_u4 *d = reinterpret_cast<wb_u4 *>(dst);  // d_ops is 16-B aligned, an op is 32 bytes
+    d[0] = a;
+    d[1] = b;
+}
+
+// One lane: op k of the record goes straight to d_ops[base + k].
+struct WbLaneSink {
+    lv_wb_op *ops;
+    uint64_t base, cap;
+    __device__ __forceinline__ void put(uint64_t k, uint64_t tag, uint64_t koff, uint64_t voff, uint32_t klen,
+                                        uint32_t vlen) {
+        const uint64_t at = base + k;
+        if (at < cap) wb_store_op(ops + at, tag, koff, voff, klen, vlen);  // (the status said it fits)
+    }
+    __device__ __forceinline__ void finish(uint64_t) {}
+};
+
+// One wave: lane k % 64 keeps op k; after every 64th op, and at the end, the
+// lanes store what they hold -- 64 consecutive 32-B entries, in 16-B stores.
+struct WbWaveSink {
+    lv_wb_op *ops;
+    uint64_t base, cap;
+    uint32_t lane;
+    uint64_t tag, koff, voff;
+    uint32_t klen, vlen;
+    __device__ __forceinline__ void flush(uint64_t first, uint32_t count) {
+        const uint64_t at = base + first + lane;
+        if (lane < count && at < cap) wb_store_op(ops + at, tag, koff, voff, klen, vlen);
+    }
+    __device__ __forceinline__ void put(uint64_t k, uint64_t t, uint64_t ko, uint64_t vo, uint32_t kl, uint32_t vl) {
+        const uint32_t slot = static_cast<uint32_t>(k) & 63u;
+        if (slot == lane) {
+            tag = t;
+            koff = ko;
+            voff = vo;
+            klen = kl;
+            vlen = vl;
+        }
+        if (slot == 63u) flush(k - 63u, 64u);
+    }
+    __device__ __forceinline__ void finish(uint64_t found) {
+        const uint32_t rest = static_cast<uint32_t>(found) & 63u;
+        if (rest) flush(found - rest, rest);
+    }
+};
+
+// ---- the walk -------------------------------------------------------------
+struct WbRes {
+    uint64_t found, key_bytes, val_bytes, seq;
+    uint32_t status;
+};
+
+// coding.rs:186-204 and :294-305 over the record's remaining input
+// [*pos, n): LV_WB_OK with *len and *pos past the length, or the error.
+template <class Src>
+__device__ __forceinline__ uint32_t wb_varstring(Src &src, uint64_t off, uint64_t n, uint64_t *pos, uint32_t *len) {
+    uint32_t result = 0;
+    uint64_t p = *pos;
+    bool done = false;
+    for (uint32_t shift = 0; shift <= 28 && p < n; shift += 7) {
+        const uint32_t b = src.byte(off + p);
+        ++p;
+        result |= (b & 0x7fu) << shift;  // bits above 31 of the fifth byte fall off
+        if (!(b & 0x80u)) {
+            done = true;
+            break;
+        }
+    }
+    if (!done) return LV_WB_BAD_VARINT;
+    if (n - p < result) return LV_WB_BAD_LENGTH;
+    *pos = p;
+    *len = result;
+    return LV_WB_OK;
+}
+
+// WriteBatch::iterate over d_payload[off, off + n), the extent already known
+// to lie inside the payload.  Reads only bytes of the record (through src).
+template <class Src, class Sink>
+__device__ __forceinline__ WbRes wb_walk(Src &src, Sink &sink, uint64_t off, uint64_t n) {
+    WbRes r{0, 0, 0, 0, LV_WB_OK};
+    if (n < LV_WB_HEADER_SIZE) {
+        r.status = LV_WB_TOO_SMALL;
+        return r;
+    }
+    uint64_t seq = 0;
+    uint32_t count = 0;
+    for (uint32_t i = 0; i < 8; ++i) seq |= static_cast<uint64_t>(src.byte(off + i)) << (8 * i);
+    for (uint32_t i = 0; i < 4; ++i) count |= src.byte(off + 8 + i) << (8 * i);
+    r.seq = seq;
+    uint64_t pos = LV_WB_HEADER_SIZE;
+    while (pos < n) {
+        const uint32_t tag = src.byte(off + pos);
+        ++pos;
+        if (tag > LV_WB_TYPE_VALUE) {
+            r.status = LV_WB_BAD_TAG;
+            break;
+        }
+        uint32_t klen = 0, vlen = 0;
+        if ((r.status = wb_varstring(src, off, n, &pos, &klen)) != LV_WB_OK) break;
+        const uint64_t koff = off + pos;
+        pos += klen;
+        uint64_t voff = off + pos;
+        if (tag == LV_WB_TYPE_VALUE) {
+            if ((r.status = wb_varstring(src, off, n, &pos, &vlen)) != LV_WB_OK) break;
+            voff = off + pos;
+            pos += vlen;
+        }
+        sink.put(r.found, ((seq + r.found) << 8) | tag, koff, voff, klen, vlen);
+        ++r.found;
+        r.key_bytes += klen;
+        r.val_bytes += vlen;
+    }
+    sink.finish(r.found);
+    if (r.status == LV_WB_OK && r.found != count) r.status = LV_WB_WRONG_COUNT;
+    return r;
+}
+
+__device__ __forceinline__ uint64_t wb_shfl64(uint64_t v, uint32_t src) {
+    const uint32_t lo = __shfl(static_cast<uint32_t>(v), static_cast<int>(src));
+    const uint32_t hi = __shfl(static_cast<uint32_t>(v >> 32), static_cast<int>(src));
+    return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+
+__device__ __forceinline__ uint64_t wb_wave_sum(uint64_t v) {
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) {
+        const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), static_cast<int>(d));
+        const uint32_t hi = __shfl_xor(static_cast<uint32_t>(v >> 32), static_cast<int>(d));
+        v += (static_cast<uint64_t>(hi) << 32) | lo;
+    }
+    return v;
+}
+__device__ __forceinline__ uint64_t wb_wave_max(uint64_t v) {
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) {
+        const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), static_cast<int>(d));
+        const uint32_t hi = __shfl_xor(static_cast<uint32_t>(v >> 32), static_cast<int>(d));
+        const uint64_t o = (static_cast<uint64_t>(hi) << 32) | lo;
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// Record r's extent and class.  cls: 0 nothing to walk (beyond n, or out of
+// range), 1 lane, 2 wave.
+__device__ __forceinline__ uint32_t wb_classify(const WbArgs &A, uint64_t r, uint64_t n, uint64_t *off, uint64_t *len,
+                                                uint32_t *status) {
+    *off = 0;
+    *len = 0;
+    *status = LV_WB_OK;
+    if (r >= n) return 0;
+    const uint64_t o = A.rec_off[r], l = A.rec_len[r];
+    if (o > A.payload_bytes || l > A.payload_bytes - o) {  // u64, no wrap
+        *status = LV_WB_OUT_OF_RANGE;
+        return 0;
+    }
+    *off = o;
+    *len = l;
+    return l <= kWbSmall ? 1u : 2u;
+}
+
+// Workgroup-wide exclusive scan of one u64 per thread (Hillis-Steele in LDS);
+// *total = the sum of all.
+template <uint32_t kThreads>
+__device__ __forceinline__ uint64_t wb_scan(uint64_t v, uint64_t *lds, uint64_t *total) {
+    const uint32_t t = threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+    for (uint32_t d = 1; d < kThreads; d <<= 1) {
+        const uint64_t o = t >= d ? lds[t - d] : 0ull;
+        __syncthreads();
+        v += o;
+        lds[t] = v;
+        __syncthreads();
+    }
+    const uint64_t ex = t ? lds[t - 1] : 0ull;
+    *total = lds[kThreads - 1];
+    __syncthreads();
+    return ex;
+}
+
+// Kernel 1: the count walk.  A workgroup takes a tile of kWbTile records, its
+// waves the tile's 64-record chunks.
+__global__ __launch_bounds__(kWbThreads) void wb_count(const WbArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[kWbWaves][kWbWindow + kWbWinPad];
+    __shared__ unsigned long long s_tile;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t n = wb_records(A);
+    const uint64_t ntiles = (n + kWbTile - 1) / kWbTile;
+    uint64_t kb = 0, vb = 0, bad = 0, last = 0;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        if (tid == 0) s_tile = 0;
+        __syncthreads();
+        uint64_t ops = 0;
+        for (uint32_t c = wave; c < kWbChunks; c += kWbWaves) {
+            const uint64_t r = tile * kWbTile + c * 64u + lane;
+            uint64_t off, len;
+            uint32_t status;
+            const uint32_t cls = wb_classify(A, r, n, &off, &len, &status);
+            WbRes res{0, 0, 0, 0, status};
+            if (cls == 1) {
+                WbLaneSrc src(A.payload);
+                WbNoSink sink;
+                res = wb_walk(src, sink, off, len);
+            }
+            uint64_t m = __ballot(cls == 2);
+            while (m) {  // wave-uniform
+                const uint32_t b = static_cast<uint32_t>(__builtin_ctzll(m));
+                m &= m - 1;
+                const uint64_t woff = wb_shfl64(off, b), wlen = wb_shfl64(len, b);
+                WbWaveSrc src(A.payload, s_win[wave], woff + wlen, lane);
+                WbNoSink sink;
+                const WbRes wr = wb_walk(src, sink, woff, wlen);
+                if (lane == b) res = wr;
+            }
+            if (r < n) {
+                A.cnt[r] = res.found;
+                A.st[r] = res.status;
+                ops += res.found;
+                kb += res.key_bytes;
+                vb += res.val_bytes;
+                bad += res.status != LV_WB_OK;
+                if (res.found) {
+                    const uint64_t ls = res.seq + res.found - 1;  // wrapping
+                    last = ls > last ? ls : last;
+                }
+            }
+        }
+        ops = wb_wave_sum(ops);
+        if (lane == 0 && ops) atomicAdd(&s_tile, static_cast<unsigned long long>(ops));
+        __syncthreads();
+        if (tid == 0) A.tsum[tile] = s_tile;
+        __syncthreads();
+    }
+    kb = wb_wave_sum(kb);
+    vb = wb_wave_sum(vb);
+    bad = wb_wave_sum(bad);
+    last = wb_wave_max(last);
+    if (lane == 0) {
+        if (kb) atomicAdd(&A.head->key_bytes, static_cast<unsigned long long>(kb));
+        if (vb) atomicAdd(&A.head->val_bytes, static_cast<unsigned long long>(vb));
+        if (bad) atomicAdd(&A.head->bad, static_cast<unsigned long long>(bad));
+        if (last) atomicMax(&A.head->last_seq, static_cast<unsigned long long>(last));
+    }
+}
+
+// Kernel 2 (one workgroup): the exclusive scan of the tile counts in place,
+// the totals and the status.
+__global__ __launch_bounds__(kWbScanThreads) void wb_tiles(const WbArgs A) {
+    __shared__ uint64_t s_scan[kWbScanThreads];
+    const uint32_t t = threadIdx.x;
+    const uint64_t n = wb_records(A);
+    const uint64_t ntiles = (n + kWbTile - 1) / kWbTile;
+    uint64_t carry = 0;
+    for (uint64_t base = 0; base < ntiles; base += kWbScanThreads) {
+        const uint64_t tile = base + t;
+        const uint64_t v = tile < ntiles ? A.tsum[tile] : 0ull;
+        uint64_t total;
+        const uint64_t ex = wb_scan<kWbScanThreads>(v, s_scan, &total);
+        if (tile < ntiles) A.tsum[tile] = carry + ex;
+        carry += total;
+    }
+    if (t == 0) {
+        uint64_t status = 0;
+        const bool up = A.upstream && *A.upstream;
+        if (up) status |= LV_WB_DECODE_UPSTREAM;
+        if (!up && *A.records > A.rec_cap) status |= LV_WB_DECODE_REC_OVER;
+        if (carry > A.out.op_cap) status |= LV_WB_DECODE_OP_OVER;
+        lv_wb_totals tot;
+        tot.records = up ? 0ull : *A.records;
+        tot.ops = carry;
+        tot.key_bytes = A.head->key_bytes;
+        tot.value_bytes = A.head->val_bytes;
+        tot.bad_records = A.head->bad;
+        tot.last_sequence = A.head->last_seq;
+        tot.status = status;
+        *A.out.d_totals = tot;
+        A.head->n = n;
+        A.head->status = status;
+        if (!status) A.out.d_rec_op[n] = carry;
+    }
+}
+
+// Kernel 3: the emit walk.  The scan of a tile's counts gives each record's
+// base; the records with ops are walked again, as in wb_count.
+__global__ __launch_bounds__(kWbThreads) void wb_emit(const WbArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[kWbWaves][kWbWindow + kWbWinPad];
+    __shared__ uint64_t s_scan[kWbThreads];
+    __shared__ uint64_t s_base[kWbTile];
+    if (A.head->status) return;  // only the totals are written
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t n = A.head->n;
+    const uint64_t ntiles = (n + kWbTile - 1) / kWbTile;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t first = tile * kWbTile + static_cast<uint64_t>(tid) * kWbPer;
+        uint64_t c[kWbPer], sum = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kWbPer; ++j) {
+            c[j] = first + j < n ? A.cnt[first + j] : 0ull;
+            sum += c[j];
+        }
+        uint64_t total;
+        uint64_t at = A.tsum[tile] + wb_scan<kWbThreads>(sum, s_scan, &total);
+#pragma unroll
+        for (uint32_t j = 0; j < kWbPer; ++j) {
+            s_base[tid * kWbPer + j] = at;
+            if (first + j < n) {
+                A.out.d_rec_op[first + j] = at;
+                A.out.d_rec_status[first + j] = A.st[first + j];
+            }
+            at += c[j];
+        }
+        __syncthreads();
+        for (uint32_t ch = wave; ch < kWbChunks; ch += kWbWaves) {
+            const uint64_t r = tile * kWbTile + ch * 64u + lane;
+            uint64_t off, len;
+            uint32_t status;
+            uint32_t cls = wb_classify(A, r, n, &off, &len, &status);
+            if (cls && A.cnt[r] == 0) cls = 0;  // nothing to write
+            const uint64_t base = s_base[ch * 64u + lane];
+            if (cls == 1) {
+                WbLaneSrc src(A.payload);
+                WbLaneSink sink{A.out.d_ops, base, A.out.op_cap};
+                wb_walk(src, sink, off, len);
+            }
+            uint64_t m = __ballot(cls == 2);
+            while (m) {  // wave-uniform
+                const uint32_t b = static_cast<uint32_t>(__builtin_ctzll(m));
+                m &= m - 1;
+                const uint64_t woff = wb_shfl64(off, b), wlen = wb_shfl64(len, b), wbase = wb_shfl64(base, b);
+                WbWaveSrc src(A.payload, s_win[wave], woff + wlen, lane);
+                WbWaveSink sink{A.out.d_ops, wbase, A.out.op_cap, lane, 0, 0, 0, 0, 0};
+                wb_walk(src, sink, woff, wlen);
+            }
+        }
+        __syncthreads();  // s_base is rewritten by the next tile
+    }
+}
+
+}  // namespace lvk
+
+using namespace lvh;
+
+namespace {
+
+constexpr uint64_t kMaxRecCap = 0xfffffffeull;
+constexpr uint64_t kMaxOpCap = 1ull << 58;  // op_cap * sizeof(lv_wb_op) stays far from 2^64
+
+struct WbWs {
+    size_t head, cnt, st, tsum, total;
+    uint64_t tiles;
+};
+WbWs wb_ws_layout(uint64_t cap) {
+    WbWs w;
+    w.tiles = (cap + lvk::kWbTile - 1) / lvk::kWbTile;
+    w.head = 0;
+    w.cnt = al16(sizeof(lvk::WbHead));
+    w.st = w.cnt + al16(cap * sizeof(uint64_t));
+    w.tsum = w.st + al16(cap * sizeof(uint32_t));
+    w.total = w.tsum + al16(w.tiles * sizeof(uint64_t));
+    return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t lv_write_batch_decode_workspace_bytes(size_t rec_cap) { return wb_ws_layout(rec_cap).total; }
+
+int lv_write_batch_decode_device(const uint8_t *d_payload, size_t payload_bytes, const uint64_t *d_rec_off,
+                                 const uint64_t *d_rec_len, const uint64_t *d_records,
+                                 const uint64_t *d_upstream_status, size_t rec_cap, const lv_wb_decode_out *out,
+                                 uint32_t flags, void *d_workspace, size_t workspace_bytes, void *stream) {
+    g_err.clear();
+    if (flags) return set_err(LV_ERR_INVALID, "unknown flag bits (none are defined)");
+    if (!out) return set_err(LV_ERR_INVALID, "null output descriptor");
+    if (!out->d_totals) return set_err(LV_ERR_INVALID, "null d_totals");
+    if (reinterpret_cast<uintptr_t>(out->d_totals) % 8) return set_err(LV_ERR_INVALID, "d_totals must be 8-byte aligned");
+    if (!d_records) return set_err(LV_ERR_INVALID, "null d_records");
+    if (!d_payload && payload_bytes) return set_err(LV_ERR_INVALID, "null d_payload");
+    if (rec_cap > kMaxRecCap) return set_err(LV_ERR_INVALID, "rec_cap too large for one decode (at most 2^32 - 2)");
+    if (out->op_cap > kMaxOpCap) return set_err(LV_ERR_INVALID, "op_cap too large (at most 2^58)");
+    if (rec_cap && (!d_rec_off || !d_rec_len)) return set_err(LV_ERR_INVALID, "null record array (d_rec_off / d_rec_len)");
+    if (!out->d_rec_op) return set_err(LV_ERR_INVALID, "null d_rec_op");
+    if (reinterpret_cast<uintptr_t>(out->d_rec_op) % 8) return set_err(LV_ERR_INVALID, "d_rec_op must be 8-byte aligned");
+    if (rec_cap && !out->d_rec_status) return set_err(LV_ERR_INVALID, "null d_rec_status");
+    if (out->op_cap && !out->d_ops) return set_err(LV_ERR_INVALID, "null d_ops");
+    if (reinterpret_cast<uintptr_t>(out->d_ops) % 16) return set_err(LV_ERR_INVALID, "d_ops must be 16-byte aligned");
+    if (!d_workspace) return set_err(LV_ERR_INVALID, "null workspace");
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
+    const WbWs ws = wb_ws_layout(rec_cap);
+    if (workspace_bytes < ws.total) return set_err(LV_ERR_INVALID, "workspace too small");
+    {
+        const uintptr_t o = reinterpret_cast<uintptr_t>(out->d_ops), p = reinterpret_cast<uintptr_t>(d_payload);
+        const uint64_t ob = static_cast<uint64_t>(out->op_cap) * sizeof(lv_wb_op);
+        if (payload_bytes && ob && o < p + payload_bytes && p < o + ob)
+            return set_err(LV_ERR_INVALID, "d_ops overlaps d_payload");
+    }
+    DevCtx *c = nullptr;
+    if (int rc = current_ctx(&c)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t *wb = static_cast<uint8_t *>(d_workspace);
+
+    lvk::WbArgs A{};
+    A.payload = d_payload;
+    A.payload_bytes = payload_bytes;
+    A.rec_off = d_rec_off;
+    A.rec_len = d_rec_len;
+    A.records = d_records;
+    A.upstream = d_upstream_status;
+    A.rec_cap = rec_cap;
+    A.out = *out;
+    A.head = reinterpret_cast<lvk::WbHead *>(wb + ws.head);
+    A.cnt = reinterpret_cast<uint64_t *>(wb + ws.cnt);
+    A.st = reinterpret_cast<uint32_t *>(wb + ws.st);
+    A.tsum = reinterpret_cast<uint64_t *>(wb + ws.tsum);
+
+    const uint64_t cus = static_cast<uint64_t>(c->cus > 0 ? c->cus : 1);
+    const dim3 b(lvk::kWbThreads);
+    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(ws.tiles, 16 * cus));
+    LV_HIP(hipMemsetAsync(A.head, 0, sizeof(lvk::WbHead), s));
+    if (grid) hipLaunchKernelGGL(lvk::wb_count, dim3(grid), b, 0, s, A);
+    hipLaunchKernelGGL(lvk::wb_tiles, dim3(1), dim3(lvk::kWbScanThreads), 0, s, A);
+    if (grid) hipLaunchKernelGGL(lvk::wb_emit, dim3(grid), b, 0, s, A);
+    g_kernel = "wb_count+wb_tiles+wb_emit";
+    return check_launch();
+}
+
+}  // extern "C"

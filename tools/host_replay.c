@@ -11,6 +11,7 @@
 #include <time.h>
 
 #include "../include/lvgpu/wal.h"
+#include "../include/lvgpu/write_batch.h"
 
 static double now_s(void) {
     struct timespec t;
@@ -63,6 +64,37 @@ double lv_replay_scan_pipelined(const uint8_t *log, size_t bytes, int device, in
         const double el = now_s() - t0;
         if (rc) return -1.0;
         if (best < 0 || el < best) best = el;
+    }
+    return best;
+}
+
+/* tools/bench_write_batch.py's host route: lv_write_batch_iterate over every
+ * record payload[off[r], off[r] + len[r]) on one core, the ops written end to
+ * end into `ops` (capacity op_cap) as lv_write_batch_decode_device lays them
+ * out; best of `reps` passes in seconds, *total = the ops of one pass, *bad =
+ * its records with a status other than LV_WB_OK (-1.0 if op_cap is too small). */
+double lv_replay_write_batch(const uint8_t *payload, const uint64_t *off, const uint64_t *len, size_t n, lv_wb_op *ops,
+                             size_t op_cap, int reps, uint64_t *total, uint64_t *bad) {
+    double best = -1.0;
+    for (int r = 0; r < reps; ++r) {
+        const double t0 = now_s();
+        uint64_t at = 0, nbad = 0;
+        for (size_t i = 0; i < n; ++i) {
+            size_t found = 0;
+            const uint32_t st = lv_write_batch_iterate(payload + off[i], (size_t)len[i], ops + at, op_cap - at, &found,
+                                                       NULL, NULL);
+            if (found > op_cap - at) return -1.0;
+            for (size_t k = 0; k < found; ++k) {  /* offsets into the payload, as on the device */
+                ops[at + k].key_off += off[i];
+                ops[at + k].val_off += off[i];
+            }
+            at += found;
+            nbad += st != LV_WB_OK;
+        }
+        const double el = now_s() - t0;
+        if (best < 0 || el < best) best = el;
+        *total = at;
+        *bad = nbad;
     }
     return best;
 }
