@@ -30,7 +30,9 @@
     defined(LVK_PIPE_FIRST_MB) || \
     defined(LVK_MEMCPY_THREADS) || \
     defined(LVK_PIPE_COPY_THREADS) || \
-    defined(LVK_WAL_UNSORT))
+    defined(LVK_WAL_UNSORT) || \
+    defined(LVK_MT_TILE) || \
+    defined(LVK_MT_PREFIX))
 #error "LVK_* kernel switches select untested code paths; only experiment variants (LVK_EXPERIMENT_BUILD, tools/build_variant.sh) may set them"
 #endif
 
@@ -84,4 +86,10 @@
 #endif
 #ifndef LVK_WAL_UNSORT  // WAL scan: CRCs stored by sorted position, then written in log order (wal_unsort)
 #define LVK_WAL_UNSORT 1
+#endif
+#ifndef LVK_MT_TILE  // memtable build: entries per tile (LDS sort, merge output tile); a power of two >= 256 (r09, 32-B entries: 512 is 3-6 % faster than 1,024, 256 is 28 % slower)
+#define LVK_MT_TILE 512
+#endif
+#ifndef LVK_MT_PREFIX  // memtable build: key bytes held in a sort entry, 8 (16-B entries) or 16 (32-B entries) (r09: 16 is 3.5x faster on "user:" keys, 2.2x slower on random ones)
+#define LVK_MT_PREFIX 16
 #endif
