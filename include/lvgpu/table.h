@@ -19,6 +19,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "memtable.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -62,6 +64,172 @@ int lv_sst_verify_blocks_device(const uint8_t *d_file, uint64_t file_bytes, cons
  * the statuses back (end-to-end path). */
 int lv_sst_verify_blocks_host(const uint8_t *file, uint64_t file_bytes, const uint64_t *handles, size_t n,
                               uint32_t *status, int device);
+
+/* ---- Build: the sorted memtable to an SSTable image ------------------------
+ *
+ * The level-0 flush.  lv_sst_build_device walks the memtable
+ * lv_memtable_build_device left in HBM (memtable.h) in d_order order and
+ * writes a complete table file image into d_file: data blocks, a metaindex
+ * block, an index block, every block's trailer, the footer.  Every entry is
+ * written: shadowed versions, deletions and exact duplicates stay.
+ *
+ * Parity.  The reference stops at table/format.rs (BlockHandle, Footer, the
+ * magic number): it has no BlockBuilder, no TableBuilder and no
+ * FindShortestSeparator.  The block and index layout below is therefore
+ * upstream C++ LevelDB's, as the trailer's (above) and the memtable order's
+ * (memtable.h) are.  No LevelDB library was available to open an image, so
+ * "a stock LevelDB opens it" is UNPINNED.  What pins the format: the worked
+ * example below (tests/golden/sst_build_one_entry.json), an independent Python
+ * model with a reader (tests/sst_build_cases.py), lv_sst_footer_decode and
+ * lv_sst_verify_blocks_device.
+ *
+ * Options: block_size (default 4096), restart_interval (default 16); no
+ * compression (type byte 0), no filter policy.  A NULL opt means the defaults.
+ *
+ * An entry's key is the internal key: the user key, then the tag as 8
+ * little-endian bytes.
+ *
+ * Data block (BlockBuilder).  State: buffer, restarts = [0], counter = 0,
+ * last_key = "".  add(key, value): if counter < restart_interval, shared =
+ * the common-prefix length of last_key and key over internal-key bytes (it may
+ * run through the user key into the tag, or from one key's tag into the next
+ * key's user bytes); otherwise push len(buffer) onto restarts, counter = 0,
+ * shared = 0.  Append varint32(shared), varint32(len(key) - shared),
+ * varint32(len(value)), key[shared:], value; last_key = key; ++counter.
+ * estimate = len(buffer) + 4 * len(restarts) + 4.  finish() appends every
+ * restart as fixed32 LE, then len(restarts) as fixed32 LE.
+ *
+ * Table (TableBuilder).  add(key, value): if an index entry is pending, add
+ * (shortest_separator(last_key, key), handle encoding of the pending handle)
+ * to the index block and clear it; last_key = key; add the entry to the data
+ * block; if estimate >= block_size (checked after the add, so a block holds
+ * at least one entry) finish the block, write it and set pending.  Writing a
+ * block at offset: the handle is {offset, len(raw)}; the file gets raw, the
+ * type byte 0 and LE32(mask(crc32c(raw || type))); offset += len(raw) + 5.
+ * finish(): flush the open data block if it is not empty; write the metaindex
+ * block, an empty BlockBuilder (the 8 bytes 00 00 00 00 01 00 00 00); if an
+ * index entry is pending add (short_successor(last_key), handle encoding);
+ * write the index block, a BlockBuilder with restart_interval = 1; write the
+ * footer, lv_sst_footer_encode(metaindex, index).
+ *
+ * Separators.  u(k) is the user key of internal key k; MAXTAG is
+ * ((2^56 - 1) << 8) | 1, the bytes 01 ff ff ff ff ff ff ff.
+ *   shortest_separator(a, b): d = the common-prefix length of u(a) and u(b).
+ *     If d >= min(len u(a), len u(b)): a.  Otherwise c = u(a)[d]; if c < 0xff
+ *     and c + 1 < u(b)[d]: u(a)[:d] + byte(c + 1) + MAXTAG; otherwise a.
+ *   short_successor(a): i = the first index with u(a)[i] != 0xff; none (the
+ *     empty key included): a.  Otherwise t = u(a)[:i] + byte(u(a)[i] + 1); if
+ *     len(t) < len(u(a)): t + MAXTAG, else a.
+ *
+ * Worked example: one entry, key "k", sequence 1, VALUE, value "v", defaults.
+ *   [0,21)    data block 00 09 01 6b 01 01 00 00 00 00 00 00 76 | 00 00 00 00
+ *             | 01 00 00 00          [21,26)  its trailer
+ *   [26,34)   the metaindex block    [34,39)  its trailer
+ *   [39,61)   index block 00 09 02 6b 01 01 00 00 00 00 00 00 00 15 |
+ *             00 00 00 00 | 01 00 00 00      [61,66)  its trailer
+ *   [66,114)  footer 1a 08 27 16, zero padding to 40 bytes, the magic
+ *
+ * Inputs.  d_payload, payload_bytes, d_ops and op_cap are those of the
+ * memtable build; d_order and *d_mt_totals are what it wrote.  *d_mt_totals is
+ * read on the device in stream order; entries is never read on the host.
+ *
+ * Outputs.  d_file[0, file_bytes) is the image.  d_handles holds
+ * {offset, size} pairs of the data blocks in file order, then the metaindex
+ * block, then the index block: data_blocks + 2 pairs, directly usable by
+ * lv_sst_verify_blocks_device; the caller provides room for block_cap + 2
+ * pairs.  *d_totals is always written.  The statuses are bits and may
+ * combine; on any of them no byte of d_file or d_handles is written:
+ *   NO_TABLE     the memtable's status is not 0 (or its entries exceed
+ *                op_cap, or an order index or an extent is out of range:
+ *                not the memtable build's arguments); entries = 0.
+ *   HANDLE_OVER  data_blocks > block_cap; the true data_blocks and file_bytes
+ *                are still reported.
+ *   FILE_OVER    file_bytes > file_cap; the true file_bytes is reported, so
+ *                the caller can retry once.
+ *   BLOCK_LARGE  some block's raw size is >= 2^32 - 1, which the seal kernel
+ *                rejects.  Sizes are computed in u64: no length wraps.
+ * With status 0 no byte of d_file at or beyond file_bytes is written.  An
+ * empty memtable (entries == 0, status 0) writes nothing and reports
+ * file_bytes = 0, data_blocks = 0 (upstream's BuildTable leaves no file).
+ *
+ * lv_sst_build_file_bound returns a file_cap that always suffices when the
+ * ops' key and value extents are disjoint, as lv_write_batch_decode_device's
+ * are (saturating at 2^64 - 1).  With n = op_cap entries and B <= n blocks:
+ *   data entries   sum(key_len + val_len) <= payload_bytes, plus per entry at
+ *                  most 15 bytes of varints, 8 tag bytes and 4 bytes of its
+ *                  restart (restart_interval >= 1): payload_bytes + 27 n;
+ *   per data block 4 (the restart count) + 5 (the trailer): 9 n;
+ *   index          one entry per block: a key no longer than the block's last
+ *                  (the index keys together <= payload_bytes) + 8 tag bytes +
+ *                  7 of varints + at most 20 of handle + 4 of restart:
+ *                  payload_bytes + 39 n, and 4 + 5 for its count and trailer;
+ *   metaindex 8 + 5, footer 48.
+ * so the bound is 2 payload_bytes + 75 n + 70.
+ *
+ * Arguments, checked on the host before any device call (LV_ERR_INVALID,
+ * lv_last_error): NULL pointers (d_payload only with payload_bytes == 0, d_ops
+ * and d_order only with op_cap == 0, d_file only with file_cap == 0), d_ops
+ * and d_file 16-byte aligned, d_handles, d_totals and d_mt_totals 8-byte
+ * aligned, d_order 4-byte aligned, d_workspace 16-byte aligned and >=
+ * lv_sst_build_workspace_bytes(op_cap, block_cap) bytes, flags == 0,
+ * 1 <= restart_interval <= 1024, 1 <= block_size <= 2^30,
+ * op_cap <= 2^32 - 2, block_cap <= 2^32 - 4, and d_file[0, file_cap) and
+ * d_handles[0, 2 (block_cap + 2)) must not overlap d_payload, d_ops, d_order
+ * or each other.  Without a usable GPU a well-formed call fails with the
+ * runtime's error: there is no host fallback.
+ *
+ * Stream-ordered, no host synchronisation, staging or stream queries.  The
+ * launch sequence depends only on values the host holds, never on the
+ * device-side counts: op_cap and block_cap size the grids and the number of
+ * passes, restart_interval the grid of the first carry scan (one wave per
+ * residue), and file_cap == 0 leaves out the trailer launches, which could
+ * write nothing.  In order: init; entry sizes with a tile-local scan; the tile
+ * carries; the successor of every entry; ceil(log2(op_cap)) pointer-doubling
+ * passes that mark the block starts (none for op_cap <= 1); the block layout
+ * (two tile scans with their carries); the plan, which decides the status
+ * once; the entry emit; the index, metaindex, footer and handles; then, with
+ * file_cap != 0, the seal (lv_sst_seal_blocks_device's own kernel over a
+ * handle array padded to block_cap + 2 in the workspace) for the data blocks
+ * and the metaindex block, lv_crc32c_batch_device_ws over the index block as
+ * one buffer, which grows with the table, and a one-thread trailer write.
+ * With op_cap == 0 only the init, the plan and the handle kernel run.
+ * Launches whose work lies beyond the device-side counts return at once.  No
+ * workgroup waits on another inside a launch.  It may be captured into a HIP
+ * graph once the device has been initialised. */
+typedef struct lv_sst_build_options { uint32_t block_size, restart_interval; } lv_sst_build_options;
+typedef struct lv_sst_build_totals {   /* device memory, 8-B aligned, always written */
+    uint64_t entries, data_blocks, file_bytes,
+             metaindex_offset, metaindex_size, index_offset, index_size, status;
+} lv_sst_build_totals;
+#define LV_SST_BUILD_NO_TABLE     1u
+#define LV_SST_BUILD_HANDLE_OVER  2u
+#define LV_SST_BUILD_FILE_OVER    4u
+#define LV_SST_BUILD_BLOCK_LARGE  8u
+#define LV_SST_DEFAULT_BLOCK_SIZE 4096u
+#define LV_SST_DEFAULT_RESTART_INTERVAL 16u
+#define LV_SST_MAX_BLOCK_SIZE (1u << 30)
+#define LV_SST_MAX_RESTART_INTERVAL 1024u
+
+size_t lv_sst_build_workspace_bytes(size_t op_cap, size_t block_cap);
+uint64_t lv_sst_build_file_bound(uint64_t payload_bytes, uint64_t op_cap, const lv_sst_build_options *opt);
+int lv_sst_build_device(const uint8_t *d_payload, size_t payload_bytes, const lv_wb_op *d_ops,
+                        const uint32_t *d_order, const lv_mt_totals *d_mt_totals, size_t op_cap,
+                        const lv_sst_build_options *opt,
+                        uint8_t *d_file, uint64_t file_cap, uint64_t *d_handles, size_t block_cap,
+                        lv_sst_build_totals *d_totals, uint32_t flags,
+                        void *d_workspace, size_t workspace_bytes, void *stream);
+/* The host twin (pure, no GPU): a serial restatement of the format above over
+ * host memory with the same statuses; trailers by lv_crc32c_extend.  The entry
+ * count is mt_totals->entries.  file == NULL with file_cap == 0 is a sizing
+ * pass: nothing is written and FILE_OVER is not reported (nor HANDLE_OVER
+ * when handles == NULL and block_cap == 0); the totals are the true ones.
+ * Returns 0, or LV_ERR_INVALID for a NULL pointer the call needs, options out
+ * of range or more than 2^32 - 2 entries. */
+int lv_sst_build_host(const uint8_t *payload, size_t payload_bytes, const lv_wb_op *ops,
+                      const uint32_t *order, const lv_mt_totals *mt_totals,
+                      const lv_sst_build_options *opt,
+                      uint8_t *file, uint64_t file_cap, uint64_t *handles, size_t block_cap,
+                      lv_sst_build_totals *totals);
 
 #ifdef __cplusplus
 }

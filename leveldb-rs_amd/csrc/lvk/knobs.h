@@ -32,7 +32,10 @@
     defined(LVK_PIPE_COPY_THREADS) || \
     defined(LVK_WAL_UNSORT) || \
     defined(LVK_MT_TILE) || \
-    defined(LVK_MT_PREFIX))
+    defined(LVK_MT_PREFIX) || \
+    defined(LVK_SB_TILE) || \
+    defined(LVK_SB_WAVE_COPY) || \
+    defined(LVK_SB_COPY_LANES))
 #error "LVK_* kernel switches select untested code paths; only experiment variants (LVK_EXPERIMENT_BUILD, tools/build_variant.sh) may set them"
 #endif
 
@@ -92,4 +95,13 @@
 #endif
 #ifndef LVK_MT_PREFIX  // memtable build: key bytes held in a sort entry, 8 (16-B entries) or 16 (32-B entries) (r09: 16 is 3.5x faster on "user:" keys, 2.2x slower on random ones)
 #define LVK_MT_PREFIX 16
+#endif
+#ifndef LVK_SB_TILE  // SSTable build: entries per scan tile (sizes, layout, index); a multiple of 256, >= the largest restart interval (1,024)
+#define LVK_SB_TILE 1024
+#endif
+#ifndef LVK_SB_WAVE_COPY  // SSTable build: a key suffix or value of at least this many bytes is copied by its wave, not its lane (>= 16)
+#define LVK_SB_WAVE_COPY 64
+#endif
+#ifndef LVK_SB_COPY_LANES  // SSTable build: lanes of a wave that share one such copy (16, 32 or 64; 64 / this many copies run at a time)
+#define LVK_SB_COPY_LANES 16
 #endif

@@ -1,0 +1,311 @@
+// The host twin of sst_build.hip (include/lvgpu/table.h): the sorted memtable
+// to an SSTable image, as a serial restatement of upstream LevelDB's
+// BlockBuilder / TableBuilder (the header spells the format out).  Host only,
+// no GPU; the model-independent check of the device path and the baseline of
+// tools/bench_sst_build.py.  Two runs of one serial walk: the first sizes the
+// table and decides the status, the second writes (the index block's place in
+// the file is known only after the first).
+#include <cstring>
+#include <optional>
+#include <vector>
+
+#include "../../include/lvgpu/crc32c.h"
+#include "../../include/lvgpu/table.h"
+
+namespace {
+
+constexpr uint64_t kMaxOps = 0xfffffffeull;
+constexpr uint64_t kLargeBlock = 0xffffffffull;  // raw sizes from here on: sst_in_range refuses them
+const uint8_t kMaxTag[8] = {0x01, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff};
+
+struct IKey {  // an internal key: ulen user bytes at k, then the 8 tag bytes
+    const uint8_t *k;
+    uint64_t ulen;
+    uint8_t tag[8];
+    uint64_t len() const { return ulen + 8; }
+    uint8_t at(uint64_t i) const { return i < ulen ? k[i] : tag[i - ulen]; }
+};
+
+void put_tag(uint8_t *dst, uint64_t tag) {
+    for (int i = 0; i < 8; ++i) dst[i] = static_cast<uint8_t>(tag >> (8 * i));
+}
+
+uint64_t varint_len(uint64_t v) {
+    uint64_t n = 1;
+    while (v >= 128) {
+        v >>= 7;
+        ++n;
+    }
+    return n;
+}
+
+// where the bytes go: nowhere (sizing) or into the file
+struct Sink {
+    uint8_t *file;  // NULL: sizing
+    void bytes(uint64_t at, const uint8_t *src, uint64_t n) const {
+        if (file && n) std::memcpy(file + at, src, n);
+    }
+    uint64_t varint(uint64_t at, uint64_t v) const {
+        const uint64_t n = varint_len(v);
+        if (file) {
+            uint8_t *p = file + at;
+            while (v >= 128) {
+                *p++ = static_cast<uint8_t>(v | 0x80);
+                v >>= 7;
+            }
+            *p = static_cast<uint8_t>(v);
+        }
+        return n;
+    }
+    void fixed32(uint64_t at, uint64_t v) const {
+        if (file)
+            for (int i = 0; i < 4; ++i) file[at + i] = static_cast<uint8_t>(v >> (8 * i));
+    }
+    void trailer(uint64_t off, uint64_t size) const {
+        if (!file) return;
+        const uint8_t type = LV_SST_NO_COMPRESSION;
+        const uint32_t crc = lv_crc32c_mask(lv_crc32c_extend(lv_crc32c_extend(0, file + off, size), &type, 1));
+        file[off + size] = type;
+        fixed32(off + size + 1, crc);
+    }
+};
+
+// A BlockBuilder writing at file offset `base`.
+struct Block {
+    const Sink &out;
+    uint64_t base, interval;
+    uint64_t buffer = 0, counter = 0;
+    std::vector<uint64_t> restarts{0};
+    bool has_last = false;
+    IKey last{};
+    Block(const Sink &o, uint64_t b, uint64_t ri) : out(o), base(b), interval(ri) {}
+    bool empty() const { return buffer == 0; }
+    uint64_t estimate() const { return buffer + 4 * restarts.size() + 4; }
+    void add(const IKey &key, const uint8_t *value, uint64_t vlen) {
+        uint64_t shared = 0;
+        if (counter < interval) {
+            if (has_last) {
+                const uint64_t m = last.len() < key.len() ? last.len() : key.len();
+                while (shared < m && last.at(shared) == key.at(shared)) ++shared;
+            }
+        } else {
+            restarts.push_back(buffer);
+            counter = 0;
+        }
+        uint64_t at = base + buffer;
+        at += out.varint(at, shared);
+        at += out.varint(at, key.len() - shared);
+        at += out.varint(at, vlen);
+        if (shared < key.ulen) {
+            out.bytes(at, key.k + shared, key.ulen - shared);
+            at += key.ulen - shared;
+            out.bytes(at, key.tag, 8);
+            at += 8;
+        } else {
+            out.bytes(at, key.tag + (shared - key.ulen), key.len() - shared);
+            at += key.len() - shared;
+        }
+        out.bytes(at, value, vlen);
+        at += vlen;
+        buffer = at - base;
+        last = key;
+        has_last = true;
+        ++counter;
+    }
+    uint64_t finish() {  // the raw size
+        uint64_t at = base + buffer;
+        for (uint64_t r : restarts) {
+            out.fixed32(at, r);
+            at += 4;
+        }
+        out.fixed32(at, restarts.size());
+        return at + 4 - base;
+    }
+};
+
+// shortest_separator(a, b) / short_successor(a) as the key's parts: `copy`
+// bytes of u(a), then (bump) the byte u(a)[copy] + 1 and MAXTAG, or a's tag.
+struct Sep {
+    uint64_t copy;
+    bool bump;
+};
+Sep shortest_separator(const IKey &a, const IKey &b) {
+    const uint64_t m = a.ulen < b.ulen ? a.ulen : b.ulen;
+    uint64_t d = 0;
+    while (d < m && a.k[d] == b.k[d]) ++d;
+    if (d >= m) return {a.ulen, false};
+    const unsigned c = a.k[d];
+    if (c < 0xff && c + 1 < b.k[d]) return {d, true};
+    return {a.ulen, false};
+}
+Sep short_successor(const IKey &a) {
+    uint64_t i = 0;
+    while (i < a.ulen && a.k[i] == 0xff) ++i;
+    if (i >= a.ulen || i + 1 >= a.ulen) return {a.ulen, false};
+    return {i, true};
+}
+
+struct Run {
+    const uint8_t *payload;
+    const lv_wb_op *ops;
+    const uint32_t *order;
+    uint64_t n, block_size, interval;
+};
+
+IKey ikey(const Run &R, uint64_t i) {
+    const lv_wb_op &o = R.ops[R.order[i]];
+    IKey k;
+    k.k = R.payload + o.key_off;
+    k.ulen = o.key_len;
+    put_tag(k.tag, o.tag);
+    return k;
+}
+
+// One walk.  index_at: where the index block goes (the write pass knows it
+// from the sizing pass).  handles is NULL in a sizing pass; a write pass runs
+// only with data_blocks <= block_cap, so it has room for data_blocks + 2 pairs.
+void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, lv_sst_build_totals *t) {
+    uint64_t offset = 0, blocks = 0;
+    bool large = false;
+    Block index(out, index_at, 1);
+    std::vector<uint8_t> scratch;  // a separator's bytes: the index block keeps pointers into it
+    bool pending = false;
+    uint64_t pend_off = 0, pend_size = 0;
+    IKey last{};
+    auto add_index = [&](const Sep &s) {
+        IKey k;
+        k.k = last.k;
+        k.ulen = s.copy;
+        std::memcpy(k.tag, last.tag, 8);
+        if (s.bump) {  // u(a)[:copy] + byte + MAXTAG: the bumped byte leads the "tag" part
+            scratch.resize(s.copy + 1);
+            if (s.copy) std::memcpy(scratch.data(), last.k, s.copy);
+            scratch[s.copy] = static_cast<uint8_t>(last.k[s.copy] + 1);
+            k.k = scratch.data();
+            k.ulen = s.copy + 1;
+            std::memcpy(k.tag, kMaxTag, 8);
+        }
+        uint8_t h[LV_SST_BLOCK_HANDLE_MAX];
+        const size_t hn = lv_sst_block_handle_encode(pend_off, pend_size, h);
+        index.add(k, h, hn);
+        pending = false;
+    };
+    auto write_block = [&](Block &b) {
+        const uint64_t size = b.finish();
+        if (size >= kLargeBlock) large = true;
+        out.trailer(offset, size);
+        if (handles) {
+            handles[2 * blocks] = offset;
+            handles[2 * blocks + 1] = size;
+        }
+        pend_off = offset;
+        pend_size = size;
+        offset += size + LV_SST_TRAILER_SIZE;
+    };
+    if (R.n) {
+        std::optional<Block> data;
+        data.emplace(out, 0, R.interval);
+        for (uint64_t i = 0; i < R.n; ++i) {
+            const lv_wb_op &o = R.ops[R.order[i]];
+            const IKey key = ikey(R, i);
+            if (pending) add_index(shortest_separator(last, key));
+            last = key;
+            data->add(key, R.payload + o.val_off, o.val_len);
+            if (data->estimate() >= R.block_size) {
+                write_block(*data);
+                ++blocks;
+                pending = true;
+                data.emplace(out, offset, R.interval);
+            }
+        }
+        if (!data->empty()) {
+            write_block(*data);
+            ++blocks;
+            pending = true;
+        }
+    }
+    t->data_blocks = blocks;
+    if (!R.n) return;  // no file
+    // the metaindex block: an empty BlockBuilder
+    Block meta(out, offset, R.interval);
+    t->metaindex_offset = offset;
+    t->metaindex_size = meta.finish();
+    out.trailer(offset, t->metaindex_size);
+    if (handles) {
+        handles[2 * blocks] = offset;
+        handles[2 * blocks + 1] = t->metaindex_size;
+    }
+    offset += t->metaindex_size + LV_SST_TRAILER_SIZE;
+    if (pending) add_index(short_successor(last));
+    t->index_offset = offset;
+    t->index_size = index.finish();
+    if (t->index_size >= kLargeBlock) large = true;
+    out.trailer(offset, t->index_size);
+    if (handles) {
+        handles[2 * blocks + 2] = offset;
+        handles[2 * blocks + 3] = t->index_size;
+    }
+    offset += t->index_size + LV_SST_TRAILER_SIZE;
+    if (out.file)
+        lv_sst_footer_encode(t->metaindex_offset, t->metaindex_size, t->index_offset, t->index_size, out.file + offset);
+    t->file_bytes = offset + LV_SST_FOOTER_SIZE;
+    if (large) t->status |= LV_SST_BUILD_BLOCK_LARGE;
+}
+
+bool extent_ok(uint64_t off, uint64_t len, uint64_t bytes) { return off <= bytes && len <= bytes - off; }
+
+bool options_ok(const lv_sst_build_options *opt, uint64_t *bs, uint64_t *ri) {
+    *bs = opt ? opt->block_size : LV_SST_DEFAULT_BLOCK_SIZE;
+    *ri = opt ? opt->restart_interval : LV_SST_DEFAULT_RESTART_INTERVAL;
+    return *bs >= 1 && *bs <= LV_SST_MAX_BLOCK_SIZE && *ri >= 1 && *ri <= LV_SST_MAX_RESTART_INTERVAL;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t lv_sst_build_file_bound(uint64_t payload_bytes, uint64_t op_cap, const lv_sst_build_options *opt) {
+    (void)opt;  // the bound holds for every block_size and restart_interval (table.h)
+    if (!op_cap) return 0;
+    const unsigned __int128 b = static_cast<unsigned __int128>(payload_bytes) * 2 +
+                                static_cast<unsigned __int128>(op_cap) * 75 + 70;
+    return b > ~0ull ? ~0ull : static_cast<uint64_t>(b);
+}
+
+int lv_sst_build_host(const uint8_t *payload, size_t payload_bytes, const lv_wb_op *ops, const uint32_t *order,
+                      const lv_mt_totals *mt_totals, const lv_sst_build_options *opt, uint8_t *file, uint64_t file_cap,
+                      uint64_t *handles, size_t block_cap, lv_sst_build_totals *totals) {
+    uint64_t bs, ri;
+    if (!totals || !mt_totals || !options_ok(opt, &bs, &ri)) return LV_ERR_INVALID;
+    if ((!payload && payload_bytes) || (!file && file_cap) || (!handles && block_cap)) return LV_ERR_INVALID;
+    const bool sizing = !file && !file_cap;
+    lv_sst_build_totals t{};
+    uint64_t n = mt_totals->entries;
+    if (mt_totals->status) {
+        t.status = LV_SST_BUILD_NO_TABLE;
+        n = 0;
+    }
+    if (n > kMaxOps || (n && (!ops || !order))) return LV_ERR_INVALID;
+    for (uint64_t i = 0; i < n && !t.status; ++i) {  // not the memtable build's arguments: no table
+        const lv_wb_op &o = ops[order[i]];
+        if (!extent_ok(o.key_off, o.key_len, payload_bytes) || !extent_ok(o.val_off, o.val_len, payload_bytes))
+            t.status = LV_SST_BUILD_NO_TABLE;
+    }
+    if (t.status) {
+        *totals = t;
+        return 0;
+    }
+    t.entries = n;
+    const Run R{payload, ops, order, n, bs, ri};
+    walk(R, Sink{nullptr}, 0, nullptr, &t);
+    if (t.data_blocks > block_cap && !(sizing && !handles)) t.status |= LV_SST_BUILD_HANDLE_OVER;
+    if (t.file_bytes > file_cap && !sizing) t.status |= LV_SST_BUILD_FILE_OVER;
+    if (!t.status && file && n) {
+        lv_sst_build_totals again{};
+        walk(R, Sink{file}, t.index_offset, handles, &again);
+    }
+    *totals = t;
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,867 @@
+// lv_sst_build_device: the sorted memtable of lv_memtable_build_device written
+// as a complete SSTable image in HBM (include/lvgpu/table.h spells the format
+// out; csrc/sst_build.cc is the serial twin).
+//
+// Block boundaries are a serial chain: where block b ends decides which
+// entries of block b + 1 are restarts, and so their sizes.  The chain is cut
+// like this.  With i a position in d_order:
+//
+//   nr[i]  the encoded size of entry i when it is not a restart (its shared
+//          prefix with entry i - 1 over internal-key bytes taken off),
+//   d[i]   what it costs more as a restart (shared = 0),
+//   P      the inclusive scan of nr, S the scan of d with stride
+//          restart_interval (S[i] = d[i] + S[i - R]).
+//
+// For a block that starts at s, the buffer after entry e is
+// P[e] - P[s - 1] + S[last restart <= e] - S[s - R], its estimate that plus
+// 4 per restart plus 4, monotone in e: next(s), the first entry after the
+// block that would start at s, is a bounded binary search for every s at once.
+// The true block starts are the entries reachable from 0 along next: pointer
+// doubling marks them (a flag array extended, the jump array squared, per
+// pass).  Two more scans over the start flags give every block its id and
+// file offset, and every index entry (one per block, shared = 0) its place.
+//
+//   sb_init    one thread zeroes the call's head in the workspace.
+//   sb_sizes   per tile of kSbTile entries: shared, nr, d (every order index
+//              and extent checked: LV_SST_BUILD_NO_TABLE) and the tile-local
+//              scans of P and S in LDS, with the tile's sums.
+//   sb_carry   the exclusive scan of the tiles' sums, a wave per column (P,
+//              and one column per residue of R for S); later the same kernel
+//              over the layout's and the index's columns.
+//   sb_next    next(s) for every s.
+//   sb_reach   one doubling pass.
+//   sb_layout  per block start: raw size (BLOCK_LARGE) -> tile scans of the
+//              block count and of the bytes.
+//   sb_index   per block start: id, offset, handle (into the workspace), the
+//              separator's and so the index entry's size -> tile scan.
+//   sb_plan    one thread: the totals and the status, decided once before
+//              anything is written.
+//   sb_emit    a lane per entry: its varints, key suffix, tag bytes, value,
+//              its restart slot if it is one; a block's first entry also
+//              writes the restart count and the block's index entry.  A key
+//              suffix or value of kSbWaveCopy bytes or more is copied by
+//              kSbCopyLanes lanes of the wave (64 / kSbCopyLanes such copies at
+//              a time) in 16-byte granules of the destination's alignment.
+//   sb_tail    d_handles and the padding of the workspace copy, the
+//              metaindex block, the index's count, the footer.
+//   the seal   sst_blocks_kernel<seal> (sst.hip) over the workspace handles of
+//              the data blocks and the metaindex block, padded to
+//              block_cap + 2 with {2^64 - 1, 0}, which it skips.  The index
+//              block, which grows with the table, is a one-buffer batch of
+//              the offsets API (its long-buffer split) and sb_index_trailer.
+//
+// The launch sequence depends only on what the host holds (op_cap, block_cap,
+// restart_interval for the first carry's grid, file_cap == 0 to leave out the
+// trailer launches), never on the device-side counts.  No workgroup
+// waits on another inside a launch; every search loop is bounded.  All sizes
+// and positions are u64.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/lvgpu/crc32c.h"
+#include "../../include/lvgpu/table.h"
+#include "lv_internal.h"
+#include "lvh.h"
+#include "lvk/knobs.h"
+
+namespace lvk {
+
+constexpr uint32_t kSbTile = LVK_SB_TILE;            // entries per scan tile
+constexpr uint32_t kSbWaveCopy = LVK_SB_WAVE_COPY;   // bytes from which a copy is the wave's
+constexpr uint32_t kSbCopyLanes = LVK_SB_COPY_LANES; // lanes of a wave that share one such copy
+constexpr uint32_t kSbThreads = 256;
+constexpr uint32_t kSbPer = kSbTile / kSbThreads;
+constexpr uint32_t kSbMaxR = LV_SST_MAX_RESTART_INTERVAL;
+constexpr uint64_t kSbLarge = 0xffffffffull;  // raw sizes from here on: sst_in_range refuses them
+static_assert(kSbTile % kSbThreads == 0 && kSbTile >= kSbMaxR, "a tile holds every residue of a restart interval");
+static_assert(kSbTile * 16 <= 65536, "two u64 scan arrays fit the LDS a workgroup may declare");
+static_assert(kSbWaveCopy >= 16, "a wave copy has at least one granule");
+static_assert(kSbCopyLanes >= 16 && 64 % kSbCopyLanes == 0, "a copy's lanes cover a ragged head or tail of 15 bytes");
+
+typedef uint32_t sb_u4 __attribute__((ext_vector_type(4)));
+
+struct SbHead {  // workspace, zeroed by sb_init
+    uint32_t bad, large, go, pad;
+    unsigned long long nblocks, data_bytes, idx_bytes, meta_off, index_off, index_size;
+};
+
+struct SbArgs {
+    const uint8_t *payload;
+    uint64_t payload_bytes;
+    const lv_wb_op *ops;
+    const uint32_t *order;
+    const lv_mt_totals *mt;
+    uint64_t op_cap;
+    uint32_t bs, R;
+    uint8_t *file;
+    uint64_t file_cap;
+    uint64_t *handles;
+    uint64_t block_cap;
+    lv_sst_build_totals *totals;
+    // workspace
+    SbHead *head;
+    uint64_t *shared;        // [cap] common prefix with the entry before, over internal-key bytes
+    uint64_t *Pl, *Sl;       // [cap] tile-local inclusive scans
+    uint64_t *cP, *cS;       // [tiles], [tiles * R]: the tiles' sums, then their exclusive scans
+    uint32_t *nxt, *J[2];    // [cap] next(s); the doubling's jump arrays
+    uint8_t *F;              // [cap] block-start flags
+    uint64_t *Cl, *Bl, *Il;  // [cap] tile-local scans: block count, file bytes, index bytes
+    uint64_t *cC, *cB, *cI;  // [tiles]
+    uint32_t *blk_start;     // [block_cap]
+    uint64_t *wsh;           // [2 (block_cap + 2)] the handles the seal reads
+    uint64_t *idx_off;       // [1] the index block as a one-buffer batch of the offsets API:
+    uint32_t *idx_len;       // [1] contents || type
+    uint32_t *idx_crc;       // [1] its masked crc
+};
+
+// The entries, or 0 when there is no table to read.
+__device__ __forceinline__ uint64_t sb_entries(const SbArgs &A) {
+    const uint64_t n = A.mt->entries;
+    return (A.mt->status || n > A.op_cap) ? 0 : n;
+}
+
+__device__ __forceinline__ bool sb_extent_ok(uint64_t off, uint64_t len, uint64_t bytes) {
+    return off <= bytes && len <= bytes - off;  // u64, no wrap
+}
+
+__device__ __forceinline__ lv_wb_op sb_load_op(const lv_wb_op *p) {
+    const sb_u4 *q = reinterpret_cast<const sb_u4 *>(p);  // d_ops is 16-B aligned, an op is 32 bytes
+    const sb_u4 a = q[0], b = q[1];
+    lv_wb_op o;
+    o.tag = (static_cast<uint64_t>(a.y) << 32) | a.x;
+    o.key_off = (static_cast<uint64_t>(a.w) << 32) | a.z;
+    o.val_off = (static_cast<uint64_t>(b.y) << 32) | b.x;
+    o.key_len = b.z;
+    o.val_len = b.w;
+    return o;
+}
+
+__device__ __forceinline__ uint32_t sb_varint_len(uint64_t v) {
+    uint32_t n = 1;
+    while (v >= 128) {
+        v >>= 7;
+        ++n;
+    }
+    return n;
+}
+
+__device__ __forceinline__ uint8_t *sb_put_varint(uint8_t *p, uint64_t v) {
+    while (v >= 128) {
+        *p++ = static_cast<uint8_t>(v | 0x80);
+        v >>= 7;
+    }
+    *p++ = static_cast<uint8_t>(v);
+    return p;
+}
+
+__device__ __forceinline__ void sb_put_fixed32(uint8_t *p, uint32_t v) {
+    p[0] = static_cast<uint8_t>(v);
+    p[1] = static_cast<uint8_t>(v >> 8);
+    p[2] = static_cast<uint8_t>(v >> 16);
+    p[3] = static_cast<uint8_t>(v >> 24);
+}
+
+// Byte i of the internal key (user key at k, ulen bytes, then the tag LE).
+__device__ __forceinline__ uint32_t sb_ikey_at(const uint8_t *k, uint64_t ulen, uint64_t tag, uint64_t i) {
+    return i < ulen ? k[i] : static_cast<uint32_t>(tag >> (8 * (i - ulen))) & 0xffu;
+}
+
+// Common-prefix length of a[0, m) and b[0, m): whole 8-byte words, then bytes.
+__device__ __forceinline__ uint64_t sb_common(const uint8_t *a, const uint8_t *b, uint64_t m) {
+    uint64_t i = 0;
+    for (; i + 8 <= m; i += 8) {
+        uint64_t x, y;
+        __builtin_memcpy(&x, a + i, 8);
+        __builtin_memcpy(&y, b + i, 8);
+        if (x != y) return i + (static_cast<uint32_t>(__builtin_ctzll(x ^ y)) >> 3);  // little-endian: the lowest differing byte
+    }
+    for (; i < m && a[i] == b[i]; ++i) {
+    }
+    return i;
+}
+
+// Common-prefix length of two internal keys.
+__device__ __forceinline__ uint64_t sb_shared(const SbArgs &A, const lv_wb_op &p, const lv_wb_op &c) {
+    const uint8_t *kp = A.payload + p.key_off, *kc = A.payload + c.key_off;
+    const uint64_t m = p.key_len < c.key_len ? p.key_len : c.key_len;
+    uint64_t s = sb_common(kp, kc, m);
+    if (s < m) return s;
+    for (uint32_t k = 0; k < 8; ++k, ++s)  // the shorter key's tag bytes: at most 8 more
+        if (sb_ikey_at(kp, p.key_len, p.tag, s) != sb_ikey_at(kc, c.key_len, c.tag, s)) break;
+    return s;
+}
+
+// In-place inclusive scan of s[0, kSbTile) with stride st (s[j] += s[j - st] chains).
+__device__ __forceinline__ void sb_tile_scan(uint64_t *s, uint32_t st, uint32_t tid) {
+    for (uint32_t off = st; off < kSbTile; off <<= 1) {
+        uint64_t v[kSbPer];
+#pragma unroll
+        for (uint32_t k = 0; k < kSbPer; ++k) {
+            const uint32_t j = tid + k * kSbThreads;
+            v[k] = j >= off ? s[j - off] : 0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < kSbPer; ++k) s[tid + k * kSbThreads] += v[k];
+        __syncthreads();
+    }
+}
+
+// The global scans from the tile-local ones and the scanned carries.
+__device__ __forceinline__ uint64_t sb_P(const SbArgs &A, uint64_t i) { return A.Pl[i] + A.cP[i / kSbTile]; }
+__device__ __forceinline__ uint64_t sb_S(const SbArgs &A, uint64_t i) {
+    return A.Sl[i] + A.cS[(i / kSbTile) * A.R + i % A.R];
+}
+// len(buffer) of the block that starts at s after entry e >= s, and its restarts.
+__device__ __forceinline__ uint64_t sb_buffer(const SbArgs &A, uint64_t s, uint64_t e, uint64_t *restarts) {
+    const uint64_t k = (e - s) / A.R, last = s + k * A.R;
+    *restarts = k + 1;
+    return sb_P(A, e) - (s ? sb_P(A, s - 1) : 0) + sb_S(A, last) - (s >= A.R ? sb_S(A, s - A.R) : 0);
+}
+__device__ __forceinline__ uint64_t sb_estimate(const SbArgs &A, uint64_t s, uint64_t e) {
+    uint64_t r;
+    const uint64_t b = sb_buffer(A, s, e, &r);
+    return b + 4 * r + 4;
+}
+
+// Kernel 0 (one thread): the head.  A kernel, not a memset: the call is a
+// chain of kernel launches only, which is what a captured graph replays.
+__global__ void sb_init(const SbArgs A) {
+    SbHead h{};
+    *A.head = h;
+}
+
+// Kernel 1: sizes and the tile-local scans of P and S.
+__global__ __launch_bounds__(kSbThreads) void sb_sizes(const SbArgs A) {
+    __shared__ uint64_t s_p[kSbTile], s_s[kSbTile];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n = sb_entries(A);
+    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kSbTile;
+    if (base >= n) return;
+    const uint32_t cnt = static_cast<uint32_t>(n - base < kSbTile ? n - base : kSbTile);
+    int bad = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kSbPer; ++k) {
+        const uint32_t j = tid + k * kSbThreads;
+        uint64_t nr = 0, d = 0;
+        if (j < cnt) {
+            const uint64_t i = base + j;
+            const uint32_t oi = A.order[i], pi = i ? A.order[i - 1] : oi;
+            uint64_t sh = 0;
+            if (oi >= A.op_cap || pi >= A.op_cap) {
+                bad = 1;
+            } else {
+                const lv_wb_op o = sb_load_op(A.ops + oi), p = sb_load_op(A.ops + pi);
+                if (!sb_extent_ok(o.key_off, o.key_len, A.payload_bytes) ||
+                    !sb_extent_ok(o.val_off, o.val_len, A.payload_bytes) ||
+                    !sb_extent_ok(p.key_off, p.key_len, A.payload_bytes)) {
+                    bad = 1;
+                } else {
+                    if (i) sh = sb_shared(A, p, o);
+                    const uint64_t klen = static_cast<uint64_t>(o.key_len) + 8, vlen = o.val_len;
+                    nr = sb_varint_len(sh) + sb_varint_len(klen - sh) + sb_varint_len(vlen) + (klen - sh) + vlen;
+                    d = 1 + sb_varint_len(klen) + sb_varint_len(vlen) + klen + vlen - nr;
+                }
+            }
+            A.shared[i] = sh;
+        }
+        s_p[j] = nr;
+        s_s[j] = d;
+    }
+    if (__syncthreads_or(bad)) {  // not the memtable build's arguments: no table
+        if (tid == 0) atomicOr(&A.head->bad, 1u);
+        return;
+    }
+    sb_tile_scan(s_p, 1, tid);
+    sb_tile_scan(s_s, A.R, tid);
+#pragma unroll
+    for (uint32_t k = 0; k < kSbPer; ++k) {
+        const uint32_t j = tid + k * kSbThreads;
+        if (j < cnt) {
+            A.Pl[base + j] = s_p[j];
+            A.Sl[base + j] = s_s[j];
+        }
+    }
+    if (tid == 0) A.cP[blockIdx.x] = s_p[cnt - 1];
+    for (uint32_t c = tid; c < A.R; c += kSbThreads) {  // the tile's sum of residue c: its last member's scan
+        const uint32_t r0 = static_cast<uint32_t>((c + A.R - base % A.R) % A.R);
+        A.cS[static_cast<uint64_t>(blockIdx.x) * A.R + c] = r0 < cnt ? s_s[r0 + (cnt - 1 - r0) / A.R * A.R] : 0;
+    }
+}
+
+__device__ __forceinline__ uint64_t sb_wave_incl(uint64_t v, uint32_t lane) {
+#pragma unroll
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const uint64_t u = __shfl_up(static_cast<unsigned long long>(v), o, 64);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
+// Kernel 2: the exclusive scan over the tiles of column c, in place; one wave
+// per column.  Column c is col[c + t * stride], t < tiles; its sum goes to
+// total[c] when total is not null.  which: 0 = {P, S residues} (cP is column
+// R), 1 = {block count, file bytes}, 2 = {index bytes}.
+__global__ __launch_bounds__(kSbThreads) void sb_carry(const SbArgs A, uint32_t which) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t c = blockIdx.x * (kSbThreads / 64) + (threadIdx.x >> 6);
+    const uint64_t n = sb_entries(A);
+    if (!n || A.head->bad) return;
+    const uint64_t tiles = (n + kSbTile - 1) / kSbTile;
+    uint64_t *col;
+    uint64_t stride = 1;
+    unsigned long long *total = nullptr;
+    if (which == 0) {
+        if (c > A.R) return;
+        col = c == A.R ? A.cP : A.cS + c;
+        stride = c == A.R ? 1 : A.R;
+    } else if (which == 1) {
+        if (c > 1) return;
+        col = c ? A.cB : A.cC;
+        total = c ? &A.head->data_bytes : &A.head->nblocks;
+    } else {
+        if (c > 0) return;
+        col = A.cI;
+        total = &A.head->idx_bytes;
+    }
+    uint64_t run = 0;
+    for (uint64_t t0 = 0; t0 < tiles; t0 += 64) {  // wave-uniform
+        const uint64_t t = t0 + lane;
+        const uint64_t v = t < tiles ? col[t * stride] : 0;
+        const uint64_t inc = sb_wave_incl(v, lane);
+        if (t < tiles) col[t * stride] = run + inc - v;
+        run += __shfl(static_cast<unsigned long long>(inc), 63, 64);
+    }
+    if (total && lane == 0) *total = run;
+}
+
+// Kernel 3: next(s), and the start flags' initial state.
+__global__ __launch_bounds__(kSbThreads) void sb_next(const SbArgs A) {
+    const uint64_t n = sb_entries(A);
+    const uint64_t s = static_cast<uint64_t>(blockIdx.x) * kSbThreads + threadIdx.x;
+    if (s >= n || A.head->bad) return;
+    // an entry is at least 3 bytes: bs / 3 + 1 entries reach block_size
+    uint64_t lo = s, hi = s + A.bs / 3 + 1;
+    if (hi > n - 1) hi = n - 1;
+    for (uint32_t it = 0; it < 40 && lo < hi; ++it) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (sb_estimate(A, s, mid) >= A.bs)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    A.nxt[s] = static_cast<uint32_t>(lo + 1);
+    A.F[s] = s == 0;
+}
+
+// Kernel 4: doubling pass p.  F holds the first 2^p block starts (and maybe
+// more of them: a flag set during this pass is a true start too), src is
+// next^(2^p).  A pass with 2^p >= n has nothing left to mark.
+__global__ __launch_bounds__(kSbThreads) void sb_reach(const SbArgs A, uint32_t pass) {
+    const uint64_t n = sb_entries(A);
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kSbThreads + threadIdx.x;
+    if (i >= n || A.head->bad || (1ull << pass) >= n) return;
+    const uint32_t *src = pass == 0 ? A.nxt : A.J[(pass - 1) & 1u];
+    uint32_t *dst = A.J[pass & 1u];
+    const uint32_t j = src[i];
+    if (j < n && A.F[i]) A.F[j] = 1;
+    dst[i] = j < n ? src[j] : static_cast<uint32_t>(n);
+}
+
+// Kernel 5: per block start its raw size; tile scans of the count and the bytes.
+__global__ __launch_bounds__(kSbThreads) void sb_layout(const SbArgs A) {
+    __shared__ uint64_t s_c[kSbTile], s_b[kSbTile];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n = sb_entries(A);
+    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kSbTile;
+    if (base >= n || A.head->bad) return;
+    const uint32_t cnt = static_cast<uint32_t>(n - base < kSbTile ? n - base : kSbTile);
+    uint32_t large = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kSbPer; ++k) {
+        const uint32_t j = tid + k * kSbThreads;
+        uint64_t c = 0, b = 0;
+        if (j < cnt && A.F[base + j]) {
+            const uint64_t raw = sb_estimate(A, base + j, static_cast<uint64_t>(A.nxt[base + j]) - 1);
+            large |= raw >= kSbLarge;
+            c = 1;
+            b = raw + LV_SST_TRAILER_SIZE;
+        }
+        s_c[j] = c;
+        s_b[j] = b;
+    }
+    if (large) atomicOr(&A.head->large, 1u);
+    __syncthreads();
+    sb_tile_scan(s_c, 1, tid);
+    sb_tile_scan(s_b, 1, tid);
+#pragma unroll
+    for (uint32_t k = 0; k < kSbPer; ++k) {
+        const uint32_t j = tid + k * kSbThreads;
+        if (j < cnt) {
+            A.Cl[base + j] = s_c[j];
+            A.Bl[base + j] = s_b[j];
+        }
+    }
+    if (tid == 0) {
+        A.cC[blockIdx.x] = s_c[cnt - 1];
+        A.cB[blockIdx.x] = s_b[cnt - 1];
+    }
+}
+
+// The index key of the block whose last entry is e (op o): `copy` bytes of
+// its user key, then (bump) the byte after them plus one and MAXTAG, or its
+// own tag.  shortest_separator against entry e + 1, short_successor at the end.
+struct SbSep {
+    uint64_t copy;
+    bool bump;
+};
+__device__ __forceinline__ SbSep sb_separator(const SbArgs &A, uint64_t e, uint64_t n, const lv_wb_op &o) {
+    const uint8_t *ka = A.payload + o.key_off;
+    const uint64_t la = o.key_len;
+    if (e + 1 < n) {
+        const lv_wb_op b = sb_load_op(A.ops + A.order[e + 1]);
+        const uint64_t lb = b.key_len, m = la < lb ? la : lb;
+        uint64_t d = A.shared[e + 1];  // over internal keys: the user keys' is no longer than either
+        if (d > m) d = m;
+        if (d >= m) return SbSep{la, false};
+        const uint32_t c = ka[d];
+        if (c < 0xffu && c + 1 < A.payload[b.key_off + d]) return SbSep{d, true};
+        return SbSep{la, false};
+    }
+    uint64_t i = 0;
+    while (i < la && ka[i] == 0xffu) ++i;
+    if (i >= la || i + 1 >= la) return SbSep{la, false};
+    return SbSep{i, true};
+}
+
+struct SbIndexEntry {
+    uint64_t klen, hlen, size;
+    SbSep sep;
+};
+__device__ __forceinline__ SbIndexEntry sb_index_entry(const SbArgs &A, uint64_t e, uint64_t n, const lv_wb_op &o,
+                                                       uint64_t off, uint64_t raw) {
+    SbIndexEntry x;
+    x.sep = sb_separator(A, e, n, o);
+    x.klen = x.sep.copy + (x.sep.bump ? 1 : 0) + 8;
+    x.hlen = sb_varint_len(off) + sb_varint_len(raw);
+    x.size = 1 + sb_varint_len(x.klen) + sb_varint_len(x.hlen) + x.klen + x.hlen;
+    return x;
+}
+
+// Kernel 6: per block start its id, offset and handle; the index entry's size
+// and its tile scan.
+__global__ __launch_bounds__(kSbThreads) void sb_index(const SbArgs A) {
+    __shared__ uint64_t s_i[kSbTile];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n = sb_entries(A);
+    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kSbTile;
+    if (base >= n || A.head->bad) return;
+    const uint32_t cnt = static_cast<uint32_t>(n - base < kSbTile ? n - base : kSbTile);
+#pragma unroll
+    for (uint32_t k = 0; k < kSbPer; ++k) {
+        const uint32_t j = tid + k * kSbThreads;
+        uint64_t v = 0;
+        if (j < cnt && A.F[base + j]) {
+            const uint64_t s = base + j, e = static_cast<uint64_t>(A.nxt[s]) - 1, t = s / kSbTile;
+            const uint64_t raw = sb_estimate(A, s, e);
+            const uint64_t b = A.Cl[s] + A.cC[t] - 1, off = A.Bl[s] + A.cB[t] - (raw + LV_SST_TRAILER_SIZE);
+            if (b < A.block_cap) {
+                A.blk_start[b] = static_cast<uint32_t>(s);
+                A.wsh[2 * b] = off;
+                A.wsh[2 * b + 1] = raw;
+            }
+            v = sb_index_entry(A, e, n, sb_load_op(A.ops + A.order[e]), off, raw).size;
+        }
+        s_i[j] = v;
+    }
+    __syncthreads();
+    sb_tile_scan(s_i, 1, tid);
+#pragma unroll
+    for (uint32_t k = 0; k < kSbPer; ++k) {
+        const uint32_t j = tid + k * kSbThreads;
+        if (j < cnt) A.Il[base + j] = s_i[j];
+    }
+    if (tid == 0) A.cI[blockIdx.x] = s_i[cnt - 1];
+}
+
+// Kernel 7 (one thread): the totals and the status, once, before any byte of
+// d_file or d_handles is written.
+__global__ void sb_plan(const SbArgs A) {
+    SbHead *h = A.head;
+    lv_sst_build_totals t{};
+    uint64_t n = A.mt->entries;
+    if (A.mt->status || n > A.op_cap || h->bad) {
+        t.status = LV_SST_BUILD_NO_TABLE;
+        n = 0;
+    }
+    t.entries = n;
+    if (n) {
+        const uint64_t nb = h->nblocks;
+        t.data_blocks = nb;
+        t.metaindex_offset = h->data_bytes;
+        t.metaindex_size = 8;
+        t.index_offset = t.metaindex_offset + 8 + LV_SST_TRAILER_SIZE;
+        t.index_size = h->idx_bytes + 4 * nb + 4;
+        t.file_bytes = t.index_offset + t.index_size + LV_SST_TRAILER_SIZE + LV_SST_FOOTER_SIZE;
+        if (h->large || t.index_size >= kSbLarge) t.status |= LV_SST_BUILD_BLOCK_LARGE;
+        if (nb > A.block_cap) t.status |= LV_SST_BUILD_HANDLE_OVER;
+        if (t.file_bytes > A.file_cap) t.status |= LV_SST_BUILD_FILE_OVER;
+        if (!t.status) {
+            h->go = 1;
+            h->meta_off = t.metaindex_offset;
+            h->index_off = t.index_offset;
+            h->index_size = t.index_size;
+            A.wsh[2 * nb] = t.metaindex_offset;
+            A.wsh[2 * nb + 1] = t.metaindex_size;
+            A.wsh[2 * nb + 2] = t.index_offset;
+            A.wsh[2 * nb + 3] = t.index_size;
+        }
+    }
+    *A.totals = t;
+}
+
+// len bytes from src to dst by kSbCopyLanes lanes: dst's ragged head and tail byte
+// by byte, between them 16-byte granules of dst's alignment (an unaligned
+// load, an aligned store).  len >= 16.
+__device__ __forceinline__ void sb_wave_copy(uint8_t *dst, const uint8_t *src, uint64_t len, uint32_t lane) {
+    const uint32_t head = static_cast<uint32_t>((16u - (reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u);
+    const uint64_t gran = (len - head) / 16;
+    const uint32_t tail = static_cast<uint32_t>((len - head) % 16);
+    if (lane < head) dst[lane] = src[lane];
+    for (uint64_t g = lane; g < gran; g += kSbCopyLanes) {
+        sb_u4 v;
+        __builtin_memcpy(&v, src + head + g * 16, 16);
+        *reinterpret_cast<sb_u4 *>(dst + head + g * 16) = v;
+    }
+    if (lane < tail) dst[head + gran * 16 + lane] = src[head + gran * 16 + lane];
+}
+
+// A lane's copy job: short ones it does itself, the others its wave does, a
+// group of kSbCopyLanes lanes per job and 64 / kSbCopyLanes jobs at a time.
+__device__ __forceinline__ void sb_copy(uint8_t *dst, const uint8_t *src, uint64_t len, uint32_t lane) {
+    constexpr uint32_t kGroups = 64 / kSbCopyLanes;
+    if (len < kSbWaveCopy)
+        for (uint64_t i = 0; i < len; ++i) dst[i] = src[i];
+    uint64_t todo = __ballot(len >= kSbWaveCopy);
+    const uint32_t grp = lane / kSbCopyLanes;
+    while (todo) {  // wave-uniform
+        int l = -1;  // this group's job: the grp-th lane of todo, if there is one
+        uint64_t t = todo;
+#pragma unroll
+        for (uint32_t k = 0; k < kGroups; ++k) {
+            if (k <= grp) l = t ? __ffsll(static_cast<unsigned long long>(t)) - 1 : -1;
+            t &= t - 1;  // (0 stays 0)
+        }
+        todo = t;
+        const int from = l < 0 ? 0 : l;
+        uint8_t *d = reinterpret_cast<uint8_t *>(__shfl(reinterpret_cast<unsigned long long>(dst), from, 64));
+        const uint8_t *sp = reinterpret_cast<const uint8_t *>(__shfl(reinterpret_cast<unsigned long long>(src), from, 64));
+        const uint64_t m = __shfl(static_cast<unsigned long long>(len), from, 64);
+        if (l >= 0) sb_wave_copy(d, sp, m, lane % kSbCopyLanes);
+    }
+}
+
+// Kernel 8: the entries, the restart arrays, the index entries.  Every lane of
+// a wave stays to the end: the long copies are the wave's.
+__global__ __launch_bounds__(kSbThreads) void sb_emit(const SbArgs A) {
+    if (!A.head->go) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t n = sb_entries(A);
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kSbThreads + threadIdx.x;
+    if (static_cast<uint64_t>(blockIdx.x) * kSbThreads >= n) return;
+    const bool on = i < n;
+    // three copy jobs per lane: key suffix, value, index key
+    uint8_t *kd = nullptr, *vd = nullptr, *xd = nullptr;
+    const uint8_t *ks = nullptr, *vs = nullptr, *xs = nullptr;
+    uint64_t kn = 0, vn = 0, xn = 0;
+    if (on) {
+        const lv_wb_op o = sb_load_op(A.ops + A.order[i]);
+        const uint64_t b = A.Cl[i] + A.cC[i / kSbTile] - 1;  // < block_cap: the plan checked
+        const uint64_t s = A.blk_start[b], boff = A.wsh[2 * b], raw = A.wsh[2 * b + 1];
+        const bool restart = (i - s) % A.R == 0;
+        uint64_t r;
+        const uint64_t rel = i > s ? sb_buffer(A, s, i - 1, &r) : 0;
+        const uint64_t ulen = o.key_len, klen = ulen + 8, sh = restart ? 0 : A.shared[i];
+        uint8_t *p = A.file + boff + rel;
+        p = sb_put_varint(p, sh);
+        p = sb_put_varint(p, klen - sh);
+        p = sb_put_varint(p, o.val_len);
+        if (sh < ulen) {
+            kd = p;
+            ks = A.payload + o.key_off + sh;
+            kn = ulen - sh;
+            p += kn;
+        }
+        for (uint32_t t = sh > ulen ? static_cast<uint32_t>(sh - ulen) : 0; t < 8; ++t)
+            *p++ = static_cast<uint8_t>(o.tag >> (8 * t));
+        vd = p;
+        vs = A.payload + o.val_off;
+        vn = o.val_len;
+        const uint64_t cnt = static_cast<uint64_t>(A.nxt[s]) - s, nrest = (cnt + A.R - 1) / A.R;
+        uint8_t *arr = A.file + boff + raw - 4 - 4 * nrest;  // the block's restart array
+        if (restart) sb_put_fixed32(arr + 4 * ((i - s) / A.R), static_cast<uint32_t>(rel));
+        if (i == s) {
+            sb_put_fixed32(arr + 4 * nrest, static_cast<uint32_t>(nrest));
+            // the block's index entry: shared = 0, the key, the handle
+            const uint64_t e = s + cnt - 1;
+            const lv_wb_op le = sb_load_op(A.ops + A.order[e]);
+            const SbIndexEntry x = sb_index_entry(A, e, n, le, boff, raw);
+            const uint64_t at = A.Il[i] + A.cI[i / kSbTile] - x.size;
+            uint8_t *ix = A.file + A.head->index_off;
+            sb_put_fixed32(ix + A.head->idx_bytes + 4 * b, static_cast<uint32_t>(at));
+            uint8_t *q = ix + at;
+            q = sb_put_varint(q, 0);
+            q = sb_put_varint(q, x.klen);
+            q = sb_put_varint(q, x.hlen);
+            xd = q;
+            xs = A.payload + le.key_off;
+            xn = x.sep.copy;
+            q += xn;
+            uint64_t tg = le.tag;
+            if (x.sep.bump) {
+                *q++ = static_cast<uint8_t>(xs[xn] + 1);
+                tg = (LV_MT_MAX_SEQUENCE << 8) | 1u;  // MAXTAG
+            }
+            for (uint32_t t = 0; t < 8; ++t) *q++ = static_cast<uint8_t>(tg >> (8 * t));
+            q = sb_put_varint(q, boff);
+            q = sb_put_varint(q, raw);
+        }
+    }
+    sb_copy(kd, ks, kn, lane);
+    sb_copy(vd, vs, vn, lane);
+    if (__ballot(xn != 0)) sb_copy(xd, xs, xn, lane);
+}
+
+// Kernel 9: d_handles and the workspace copy's padding; one thread writes the
+// metaindex block, the index block's restart count and type byte, and the
+// footer.  The index block is not the seal's: that kernel gives a block to a
+// group of 16 lanes, right for blocks of about block_size, while an index
+// block grows with the table (one entry per data block).  It goes to the offsets API as a one-buffer batch, whose
+// long-buffer split spreads it over the device.
+__global__ __launch_bounds__(kSbThreads) void sb_tail(const SbArgs A) {
+    const SbHead *h = A.head;
+    const uint64_t j = static_cast<uint64_t>(blockIdx.x) * kSbThreads + threadIdx.x;
+    const bool go = h->go;
+    const uint64_t nh = go ? h->nblocks + 2 : 0;
+    if (j < A.block_cap + 2) {
+        if (j < nh) {
+            A.handles[2 * j] = A.wsh[2 * j];
+            A.handles[2 * j + 1] = A.wsh[2 * j + 1];
+        }
+        if (j + 1 >= nh) {  // the seal skips a handle out of range without touching the file
+            A.wsh[2 * j] = ~0ull;
+            A.wsh[2 * j + 1] = 0;
+        }
+    }
+    if (j == 0) {
+        A.idx_off[0] = go ? h->index_off : 0;
+        A.idx_len[0] = go ? static_cast<uint32_t>(h->index_size + 1) : 0;  // (< 2^32 - 1: the plan checked)
+    }
+    if (j == 0 && go) {
+        A.file[h->index_off + h->index_size] = LV_SST_NO_COMPRESSION;
+        uint8_t *m = A.file + h->meta_off;  // an empty BlockBuilder: 00 00 00 00 01 00 00 00
+        sb_put_fixed32(m, 0);
+        sb_put_fixed32(m + 4, 1);
+        sb_put_fixed32(A.file + h->index_off + h->idx_bytes + 4 * h->nblocks, static_cast<uint32_t>(h->nblocks));
+        uint8_t *f = A.file + h->index_off + h->index_size + LV_SST_TRAILER_SIZE, *q = f;
+        q = sb_put_varint(q, h->meta_off);
+        q = sb_put_varint(q, 8);
+        q = sb_put_varint(q, h->index_off);
+        q = sb_put_varint(q, h->index_size);
+        while (q < f + 40) *q++ = 0;
+        for (uint32_t t = 0; t < 8; ++t) *q++ = static_cast<uint8_t>(LV_SST_MAGIC >> (8 * t));
+    }
+}
+
+// Kernel 10 (one thread): the index block's trailer from the batch's masked crc.
+__global__ void sb_index_trailer(const SbArgs A) {
+    const SbHead *h = A.head;
+    if (h->go) sb_put_fixed32(A.file + h->index_off + h->index_size + 1, A.idx_crc[0]);
+}
+
+}  // namespace lvk
+
+using namespace lvh;
+
+namespace {
+
+constexpr uint64_t kMaxOpCap = 0xfffffffeull;
+constexpr uint64_t kMaxBlockCap = 0xfffffffcull;
+
+struct SbWs {
+    size_t head, shared, Pl, Sl, cP, cS, nxt, J0, J1, F, Cl, Bl, Il, cC, cB, cI, blk_start, wsh, idx, crc_ws, crc_ws_bytes, total;
+    uint64_t tiles;
+};
+SbWs sb_ws_layout(uint64_t cap, uint64_t bc) {
+    SbWs w;
+    w.tiles = (cap + lvk::kSbTile - 1) / lvk::kSbTile;
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = at;
+        at += al16(bytes);
+        return o;
+    };
+    w.head = take(sizeof(lvk::SbHead));
+    w.shared = take(cap * 8);
+    w.Pl = take(cap * 8);
+    w.Sl = take(cap * 8);
+    w.cP = take(w.tiles * 8);
+    w.cS = take(w.tiles * lvk::kSbMaxR * 8);
+    w.nxt = take(cap * 4);
+    w.J0 = take(cap * 4);
+    w.J1 = take(cap * 4);
+    w.F = take(cap);
+    w.Cl = take(cap * 8);
+    w.Bl = take(cap * 8);
+    w.Il = take(cap * 8);
+    w.cC = take(w.tiles * 8);
+    w.cB = take(w.tiles * 8);
+    w.cI = take(w.tiles * 8);
+    w.blk_start = take(bc * 4);
+    w.wsh = take((bc + 2) * 16);
+    w.idx = take(16);
+    w.crc_ws_bytes = lv_crc32c_workspace_bytes(1);
+    w.crc_ws = take(w.crc_ws_bytes);
+    w.total = at;
+    return w;
+}
+
+bool overlaps(const void *a, uint64_t ab, const void *b, uint64_t bb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return ab && bb && x < y + bb && y < x + ab;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t lv_sst_build_workspace_bytes(size_t op_cap, size_t block_cap) {
+    return (op_cap > kMaxOpCap || block_cap > kMaxBlockCap) ? 0 : sb_ws_layout(op_cap, block_cap).total;
+}
+
+int lv_sst_build_device(const uint8_t *d_payload, size_t payload_bytes, const lv_wb_op *d_ops, const uint32_t *d_order,
+                        const lv_mt_totals *d_mt_totals, size_t op_cap, const lv_sst_build_options *opt,
+                        uint8_t *d_file, uint64_t file_cap, uint64_t *d_handles, size_t block_cap,
+                        lv_sst_build_totals *d_totals, uint32_t flags, void *d_workspace, size_t workspace_bytes,
+                        void *stream) {
+    g_err.clear();
+    if (flags) return set_err(LV_ERR_INVALID, "unknown flag bits (none are defined)");
+    const uint32_t bs = opt ? opt->block_size : LV_SST_DEFAULT_BLOCK_SIZE;
+    const uint32_t ri = opt ? opt->restart_interval : LV_SST_DEFAULT_RESTART_INTERVAL;
+    if (bs < 1 || bs > LV_SST_MAX_BLOCK_SIZE) return set_err(LV_ERR_INVALID, "block_size must be in [1, 2^30]");
+    if (ri < 1 || ri > LV_SST_MAX_RESTART_INTERVAL)
+        return set_err(LV_ERR_INVALID, "restart_interval must be in [1, 1024]");
+    if (!d_totals) return set_err(LV_ERR_INVALID, "null d_totals");
+    if (reinterpret_cast<uintptr_t>(d_totals) % 8) return set_err(LV_ERR_INVALID, "d_totals must be 8-byte aligned");
+    if (!d_mt_totals) return set_err(LV_ERR_INVALID, "null d_mt_totals");
+    if (reinterpret_cast<uintptr_t>(d_mt_totals) % 8)
+        return set_err(LV_ERR_INVALID, "d_mt_totals must be 8-byte aligned");
+    if (!d_payload && payload_bytes) return set_err(LV_ERR_INVALID, "null d_payload");
+    if (op_cap > kMaxOpCap) return set_err(LV_ERR_INVALID, "op_cap too large for one build (at most 2^32 - 2)");
+    if (block_cap > kMaxBlockCap) return set_err(LV_ERR_INVALID, "block_cap too large for one build (at most 2^32 - 4)");
+    if (op_cap && !d_ops) return set_err(LV_ERR_INVALID, "null d_ops");
+    if (reinterpret_cast<uintptr_t>(d_ops) % 16) return set_err(LV_ERR_INVALID, "d_ops must be 16-byte aligned");
+    if (op_cap && !d_order) return set_err(LV_ERR_INVALID, "null d_order");
+    if (reinterpret_cast<uintptr_t>(d_order) % 4) return set_err(LV_ERR_INVALID, "d_order must be 4-byte aligned");
+    if (file_cap && !d_file) return set_err(LV_ERR_INVALID, "null d_file");
+    if (reinterpret_cast<uintptr_t>(d_file) % 16) return set_err(LV_ERR_INVALID, "d_file must be 16-byte aligned");
+    if (!d_handles) return set_err(LV_ERR_INVALID, "null d_handles");
+    if (reinterpret_cast<uintptr_t>(d_handles) % 8) return set_err(LV_ERR_INVALID, "d_handles must be 8-byte aligned");
+    if (!d_workspace) return set_err(LV_ERR_INVALID, "null workspace");
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
+    const SbWs ws = sb_ws_layout(op_cap, block_cap);
+    if (workspace_bytes < ws.total) return set_err(LV_ERR_INVALID, "workspace too small");
+    const uint64_t handle_bytes = (static_cast<uint64_t>(block_cap) + 2) * 16;
+    const struct {
+        const void *p;
+        uint64_t bytes;
+        const char *name;
+    } ins[3] = {{d_payload, payload_bytes, "d_payload"},
+                {d_ops, static_cast<uint64_t>(op_cap) * sizeof(lv_wb_op), "d_ops"},
+                {d_order, static_cast<uint64_t>(op_cap) * sizeof(uint32_t), "d_order"}};
+    for (const auto &in : ins) {
+        if (overlaps(d_file, file_cap, in.p, in.bytes)) return set_err(LV_ERR_INVALID, std::string("d_file overlaps ") + in.name);
+        if (overlaps(d_handles, handle_bytes, in.p, in.bytes))
+            return set_err(LV_ERR_INVALID, std::string("d_handles overlaps ") + in.name);
+    }
+    if (overlaps(d_file, file_cap, d_handles, handle_bytes)) return set_err(LV_ERR_INVALID, "d_file overlaps d_handles");
+    DevCtx *c = nullptr;
+    if (int rc = current_ctx(&c)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t *wb = static_cast<uint8_t *>(d_workspace);
+
+    lvk::SbArgs A{};
+    A.payload = d_payload;
+    A.payload_bytes = payload_bytes;
+    A.ops = d_ops;
+    A.order = d_order;
+    A.mt = d_mt_totals;
+    A.op_cap = op_cap;
+    A.bs = bs;
+    A.R = ri;
+    A.file = d_file;
+    A.file_cap = file_cap;
+    A.handles = d_handles;
+    A.block_cap = block_cap;
+    A.totals = d_totals;
+    A.head = reinterpret_cast<lvk::SbHead *>(wb + ws.head);
+    A.shared = reinterpret_cast<uint64_t *>(wb + ws.shared);
+    A.Pl = reinterpret_cast<uint64_t *>(wb + ws.Pl);
+    A.Sl = reinterpret_cast<uint64_t *>(wb + ws.Sl);
+    A.cP = reinterpret_cast<uint64_t *>(wb + ws.cP);
+    A.cS = reinterpret_cast<uint64_t *>(wb + ws.cS);
+    A.nxt = reinterpret_cast<uint32_t *>(wb + ws.nxt);
+    A.J[0] = reinterpret_cast<uint32_t *>(wb + ws.J0);
+    A.J[1] = reinterpret_cast<uint32_t *>(wb + ws.J1);
+    A.F = wb + ws.F;
+    A.Cl = reinterpret_cast<uint64_t *>(wb + ws.Cl);
+    A.Bl = reinterpret_cast<uint64_t *>(wb + ws.Bl);
+    A.Il = reinterpret_cast<uint64_t *>(wb + ws.Il);
+    A.cC = reinterpret_cast<uint64_t *>(wb + ws.cC);
+    A.cB = reinterpret_cast<uint64_t *>(wb + ws.cB);
+    A.cI = reinterpret_cast<uint64_t *>(wb + ws.cI);
+    A.blk_start = reinterpret_cast<uint32_t *>(wb + ws.blk_start);
+    A.wsh = reinterpret_cast<uint64_t *>(wb + ws.wsh);
+    A.idx_off = reinterpret_cast<uint64_t *>(wb + ws.idx);
+    A.idx_len = reinterpret_cast<uint32_t *>(wb + ws.idx + 8);
+    A.idx_crc = reinterpret_cast<uint32_t *>(wb + ws.idx + 12);
+
+    const dim3 b(lvk::kSbThreads);
+    const uint32_t tiles = static_cast<uint32_t>(ws.tiles);
+    const uint32_t eg = static_cast<uint32_t>((static_cast<uint64_t>(op_cap) + lvk::kSbThreads - 1) / lvk::kSbThreads);
+    constexpr uint32_t kWaves = lvk::kSbThreads / 64;
+    hipLaunchKernelGGL(lvk::sb_init, dim3(1), dim3(1), 0, s, A);
+    if (tiles) {
+        hipLaunchKernelGGL(lvk::sb_sizes, dim3(tiles), b, 0, s, A);
+        hipLaunchKernelGGL(lvk::sb_carry, dim3((ri + 1 + kWaves - 1) / kWaves), b, 0, s, A, 0u);
+        hipLaunchKernelGGL(lvk::sb_next, dim3(eg), b, 0, s, A);
+        for (uint32_t p = 0; (1ull << p) < op_cap; ++p) hipLaunchKernelGGL(lvk::sb_reach, dim3(eg), b, 0, s, A, p);
+        hipLaunchKernelGGL(lvk::sb_layout, dim3(tiles), b, 0, s, A);
+        hipLaunchKernelGGL(lvk::sb_carry, dim3(1), b, 0, s, A, 1u);
+        hipLaunchKernelGGL(lvk::sb_index, dim3(tiles), b, 0, s, A);
+        hipLaunchKernelGGL(lvk::sb_carry, dim3(1), b, 0, s, A, 2u);
+    }
+    hipLaunchKernelGGL(lvk::sb_plan, dim3(1), dim3(1), 0, s, A);
+    if (tiles) hipLaunchKernelGGL(lvk::sb_emit, dim3(eg), b, 0, s, A);
+    const uint32_t hg = static_cast<uint32_t>((static_cast<uint64_t>(block_cap) + 2 + lvk::kSbThreads - 1) / lvk::kSbThreads);
+    hipLaunchKernelGGL(lvk::sb_tail, dim3(hg), b, 0, s, A);
+    if (int rc = check_launch()) return rc;
+    if (tiles && file_cap) {
+        // the trailers: the seal's own kernel over the padded handles (data blocks and metaindex) ...
+        if (int rc = lvgpu_internal::launch_sst_blocks(true, d_file, file_cap, A.wsh, nullptr,
+                                                       static_cast<size_t>(block_cap) + 2, nullptr, nullptr, stream))
+            return rc;
+        // ... and the index block as a one-buffer batch (an empty one when nothing was written)
+        if (int rc = lv_crc32c_batch_device_ws(d_file, A.idx_off, A.idx_len, nullptr, A.idx_crc, 1, LV_CRC_MASK,
+                                               wb + ws.crc_ws, ws.crc_ws_bytes, stream))
+            return rc;
+        hipLaunchKernelGGL(lvk::sb_index_trailer, dim3(1), dim3(1), 0, s, A);
+        if (int rc = check_launch()) return rc;
+    }
+    g_kernel = "sb_init+sb_sizes+sb_carry+sb_next+sb_reach+sb_layout+sb_index+sb_plan+sb_emit+sb_tail+"
+               "sst_blocks_kernel<seal>+crc32c_fused_small_kernel+sb_index_trailer";
+    return LV_OK;
+}
+
+}  // extern "C"

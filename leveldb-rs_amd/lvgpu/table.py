@@ -1,5 +1,15 @@
-"""Python mirror of src/table/format.rs (BlockHandle, Footer) and the GPU
-block-trailer seal/verify over include/lvgpu/table.h."""
+"""Python mirror of src/table/format.rs (BlockHandle, Footer), the GPU
+block-trailer seal/verify and the SSTable build over include/lvgpu/table.h.
+
+    build_host(payload, ops, order, mt_totals, block_size, restart_interval)
+                                      lv_sst_build_host: (file, handles, totals)
+    build_workspace_bytes(op_cap, block_cap)
+                                      device workspace of build_device
+    file_bound(payload_bytes, op_cap) lv_sst_build_file_bound
+    build_device(table)               lv_sst_build_device over a
+                                      lvgpu.memtable.Table; no host sync until
+                                      .sync_totals() / .file() / .handles()
+"""
 from __future__ import annotations
 
 import ctypes
@@ -7,6 +17,7 @@ import ctypes
 import numpy as np
 
 from . import LvError, _check, _dev_ptr, _stream_ptr, _torch, lib
+from .memtable import Totals as MtTotals  # lv_mt_totals
 
 MAGIC = 0xDB4775248B80FB57
 BLOCK_HANDLE_MAX_ENCODED_LENGTH = 20
@@ -128,3 +139,199 @@ def verify_blocks_host(file: bytes, handles, device: int = 0) -> np.ndarray:
     buf = ctypes.create_string_buffer(bytes(file), max(len(file), 1))
     _check(L.lv_sst_verify_blocks_host(buf, len(file), h.ctypes.data, h.shape[0], st.ctypes.data, device))
     return st
+
+
+# ---- lv_sst_build_*: the sorted memtable to an SSTable image -----------------
+BUILD_STATUS = {1: "NO_TABLE", 2: "HANDLE_OVER", 4: "FILE_OVER", 8: "BLOCK_LARGE"}  # LV_SST_BUILD_*
+BUILD_TOTALS = ("entries", "data_blocks", "file_bytes", "metaindex_offset", "metaindex_size", "index_offset",
+                "index_size", "status")
+DEFAULT_BLOCK_SIZE, DEFAULT_RESTART_INTERVAL = 4096, 16
+# csrc/lvk/knobs.h: LVK_SB_TILE (entries per scan tile of the size, layout and
+# index scans) and LVK_SB_WAVE_COPY (a key suffix or value of at least this
+# many bytes is copied by its wave, not its lane) and LVK_SB_COPY_LANES (the
+# lanes that share one such copy).  The GPU tests sweep around the first two.
+SB_TILE = 1024
+SB_WAVE_COPY = 64
+SB_COPY_LANES = 16
+
+
+class BuildOptions(ctypes.Structure):
+    """lv_sst_build_options."""
+    _fields_ = [("block_size", ctypes.c_uint32), ("restart_interval", ctypes.c_uint32)]
+
+
+class BuildTotals(ctypes.Structure):
+    """lv_sst_build_totals."""
+    _fields_ = [(n, ctypes.c_uint64) for n in BUILD_TOTALS]
+
+
+_build_bound = False
+
+
+def _bind_build():
+    global _build_bound
+    L = _bind()
+    if not _build_bound:
+        vp, sz, u64, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32
+        L.lv_sst_build_workspace_bytes.restype = sz
+        L.lv_sst_build_workspace_bytes.argtypes = [sz, sz]
+        L.lv_sst_build_file_bound.restype = u64
+        L.lv_sst_build_file_bound.argtypes = [u64, u64, vp]
+        L.lv_sst_build_device.restype = ctypes.c_int
+        L.lv_sst_build_device.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, u64, vp, sz, vp, u32, vp, sz, vp]
+        L.lv_sst_build_host.restype = ctypes.c_int
+        L.lv_sst_build_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, u64, vp, sz, vp]
+        _build_bound = True
+    return L
+
+
+def _options(block_size, restart_interval):
+    if block_size is None and restart_interval is None:
+        return None  # a NULL opt: the defaults
+    return BuildOptions(DEFAULT_BLOCK_SIZE if block_size is None else block_size,
+                        DEFAULT_RESTART_INTERVAL if restart_interval is None else restart_interval)
+
+
+def build_workspace_bytes(op_cap: int, block_cap: int) -> int:
+    return int(_bind_build().lv_sst_build_workspace_bytes(op_cap, block_cap))
+
+
+def file_bound(payload_bytes: int, op_cap: int, block_size=None, restart_interval=None) -> int:
+    """lv_sst_build_file_bound: a file_cap that suffices for disjoint extents."""
+    opt = _options(block_size, restart_interval)
+    return int(_bind_build().lv_sst_build_file_bound(payload_bytes, op_cap, ctypes.byref(opt) if opt else None))
+
+
+def build_host(payload, ops, order, mt_totals, block_size=None, restart_interval=None, *, file_cap=None,
+               block_cap=None, sizing=False, payload_bytes=None):
+    """lv_sst_build_host: (file bytes, handles [(offset, size)], totals dict).
+    sizing: file == NULL and file_cap == 0 (and no handles unless block_cap is
+    given).  file_cap / block_cap default to what a sizing pass reports.
+    payload_bytes overrides len(payload) (a sizing pass reads key bytes only).
+    With a status the file and the handles come back as the canaries they were
+    filled with, for the caller to check."""
+    from .write_batch import OP_DTYPE
+    L = _bind_build()
+    pb = bytes(payload)
+    pbuf = ctypes.create_string_buffer(pb, max(len(pb), 1))
+    pn = len(pb) if payload_bytes is None else payload_bytes
+    arr = np.ascontiguousarray(ops, dtype=OP_DTYPE)
+    order = np.ascontiguousarray(order, dtype=np.uint32)
+    mt = MtTotals(mt_totals["entries"], mt_totals["user_keys"], mt_totals["status"])
+    opt = _options(block_size, restart_interval)
+    optp = ctypes.byref(opt) if opt else None
+    tot = BuildTotals()
+
+    def call(file_p, fcap, handles_p, bcap):
+        rc = L.lv_sst_build_host(pbuf, pn, arr.ctypes.data if arr.size else None,
+                                 order.ctypes.data if order.size else None, ctypes.byref(mt), optp, file_p, fcap,
+                                 handles_p, bcap, ctypes.byref(tot))
+        if rc != 0:
+            raise LvError(f"lv_sst_build_host: {rc}")
+        return {n: int(getattr(tot, n)) for n in BUILD_TOTALS}
+
+    if sizing or file_cap is None or block_cap is None:
+        if sizing and block_cap:
+            hs = np.full(2 * (block_cap + 2), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+            return b"", hs, call(None, 0, hs.ctypes.data, block_cap)
+        t = call(None, 0, None, 0)
+        if sizing:
+            return b"", [], t
+        file_cap = t["file_bytes"] if file_cap is None else file_cap
+        block_cap = t["data_blocks"] if block_cap is None else block_cap
+    guard = 64
+    fbuf = np.full(file_cap + guard, 0xA5, dtype=np.uint8)
+    hs = np.full(2 * (block_cap + 2) + 8, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    t = call(fbuf.ctypes.data if file_cap else None, file_cap, hs.ctypes.data, block_cap)
+    if t["status"]:
+        return fbuf.tobytes(), hs, t
+    assert (fbuf[t["file_bytes"]:] == 0xA5).all(), "lv_sst_build_host wrote at or beyond file_bytes"
+    nh = t["data_blocks"] + 2 if t["file_bytes"] else 0
+    assert (hs[2 * nh:] == 0xA5A5A5A5A5A5A5A5).all(), "lv_sst_build_host wrote handles beyond its count"
+    return fbuf[: t["file_bytes"]].tobytes(), [(int(hs[2 * i]), int(hs[2 * i + 1])) for i in range(nh)], t
+
+
+class Built:
+    """Outputs of build_device, CUDA tensors written asynchronously: file_t
+    (uint8, file_cap bytes and the guard), handles_t (int64, block_cap + 2
+    pairs and the guard) and totals (int64[8], BUILD_TOTALS)."""
+
+    def __init__(self, file_t, file_cap, handles_t, block_cap, totals, keep):
+        self.file_t, self.file_cap, self.handles_t, self.block_cap, self.totals = file_t, file_cap, handles_t, block_cap, totals
+        self._keep = keep  # the workspace and the inputs, until the work has run
+        self._tot = None
+
+    def sync_totals(self, check: bool = True) -> dict:
+        """Waits for the call; the totals as a dict.  Raises LvError naming the
+        status bits if one is set (nothing was written) unless check is False."""
+        if self._tot is None:
+            torch = _torch()
+            torch.cuda.synchronize(self.totals.device)
+            t = [int(v) for v in self.totals.cpu().numpy().view(np.uint64)]
+            self._tot = dict(zip(BUILD_TOTALS, t))
+            self._keep = None
+        st = self._tot["status"]
+        if st and check:
+            names = "|".join(n for b, n in BUILD_STATUS.items() if st & b)
+            raise LvError(f"lv_sst_build_device: status {names} (totals {self._tot})")
+        return self._tot
+
+    def file(self) -> bytes:
+        """d_file[0, file_bytes) (synchronises)."""
+        n = self.sync_totals()["file_bytes"]
+        return self.file_t[:n].cpu().numpy().tobytes()
+
+    def handles(self) -> list:
+        """The data_blocks + 2 handles as (offset, size) pairs (synchronises)."""
+        t = self.sync_totals()
+        n = t["data_blocks"] + 2 if t["file_bytes"] else 0
+        h = self.handles_t[: 2 * n].cpu().numpy().view(np.uint64)
+        return [(int(h[2 * i]), int(h[2 * i + 1])) for i in range(n)]
+
+    def handles_view(self):
+        """The written handles as an (n, 2) int64 CUDA tensor for verify_blocks
+        (synchronises for the count)."""
+        t = self.sync_totals()
+        n = t["data_blocks"] + 2 if t["file_bytes"] else 0
+        return self.handles_t[: 2 * n].view(n, 2)
+
+
+def build_device(table, *, block_size=None, restart_interval=None, file_cap=None, block_cap=None, workspace=None,
+                 stream=None, fill=None, guard: int = 0, flags: int = 0):
+    """lv_sst_build_device over a lvgpu.memtable.Table (its payload, ops,
+    order and totals, read on the device).  file_cap defaults to file_bound of
+    the payload and op_cap, block_cap to op_cap (a block holds at least one
+    entry).  fill, a byte value, initialises d_file and d_handles with it first
+    and guard allocates that many more bytes behind each (canaries).  Returns a
+    Built; asynchronous on `stream`."""
+    torch = _torch()
+    L = _bind_build()
+    dev = table.payload.device
+    op_cap = int(table.op_cap)
+    if file_cap is None:
+        file_cap = file_bound(table.payload.numel(), op_cap, block_size, restart_interval)
+    if block_cap is None:
+        block_cap = op_cap
+    if workspace is None:
+        workspace = torch.empty(max(L.lv_sst_build_workspace_bytes(op_cap, block_cap), 16), dtype=torch.uint8,
+                                device=dev)
+    fbytes = (max(file_cap, 16) + guard + 15) & ~15
+    hbytes = (16 * (block_cap + 2) + guard + 7) & ~7
+    if fill is None:
+        file_t = torch.empty(fbytes, dtype=torch.uint8, device=dev)
+        handles_t = torch.empty(hbytes, dtype=torch.uint8, device=dev).view(torch.int64)
+    else:
+        file_t = torch.full((fbytes,), fill, dtype=torch.uint8, device=dev)
+        handles_t = torch.full((hbytes,), fill, dtype=torch.uint8, device=dev).view(torch.int64)
+    totals = torch.empty(len(BUILD_TOTALS), dtype=torch.int64, device=dev)
+    opt = _options(block_size, restart_interval)
+    with torch.cuda.device(dev):  # the C call runs on the current device
+        rc = L.lv_sst_build_device(_dev_ptr(table.payload, "payload"), table.payload.numel(),
+                                   _dev_ptr(table.ops_t, "ops"), _dev_ptr(table.order_t, "order"),
+                                   _dev_ptr(table.totals, "mt_totals"), op_cap, ctypes.byref(opt) if opt else None,
+                                   _dev_ptr(file_t, "file"), file_cap, _dev_ptr(handles_t, "handles"), block_cap,
+                                   _dev_ptr(totals, "totals"), flags, _dev_ptr(workspace, "workspace"),
+                                   workspace.numel(), _stream_ptr(stream))
+    if rc != 0:
+        raise LvError(f"lv_sst_build_device: {lib().lv_last_error().decode()}")
+    return Built(file_t, file_cap, handles_t, block_cap, totals, (table, workspace))
