@@ -80,8 +80,9 @@ int lv_sst_verify_blocks_host(const uint8_t *file, uint64_t file_bytes, const ui
  * (memtable.h) are.  No LevelDB library was available to open an image, so
  * "a stock LevelDB opens it" is UNPINNED.  What pins the format: the worked
  * example below (tests/golden/sst_build_one_entry.json), an independent Python
- * model with a reader (tests/sst_build_cases.py), lv_sst_footer_decode and
- * lv_sst_verify_blocks_device.
+ * model with a reader (tests/sst_build_cases.py), lv_sst_footer_decode,
+ * lv_sst_verify_blocks_device and the project's own reader (lv_sst_open_device
+ * and lv_sst_get_device, below), which opens and reads every table it writes.
  *
  * Options: block_size (default 4096), restart_interval (default 16); no
  * compression (type byte 0), no filter policy.  A NULL opt means the defaults.
@@ -230,6 +231,179 @@ int lv_sst_build_host(const uint8_t *payload, size_t payload_bytes, const lv_wb_
                       const lv_sst_build_options *opt,
                       uint8_t *file, uint64_t file_cap, uint64_t *handles, size_t block_cap,
                       lv_sst_build_totals *totals);
+
+/* ---- Open: Table::Open over an image in HBM ---------------------------------
+ *
+ * The read side.  lv_sst_open_device checks the footer and the whole index
+ * block of the image d_file[0, *d_file_bytes) and writes *d_table, which
+ * lv_sst_get_device then reads on the device.  d_file_bytes and
+ * d_upstream_status may point at &build_totals->file_bytes and
+ * &build_totals->status of an lv_sst_build_device call; both are read on the
+ * device in stream order, never on the host.  d_upstream_status may be NULL.
+ * d_file may have any byte alignment (a foreign image may sit anywhere in a
+ * buffer): every fixed32 is assembled from bytes.
+ *
+ * Written from upstream C++ LevelDB's Table::Open, Block::Iter and
+ * DecodeEntry, as the build is from its builders.  The project now opens and
+ * reads the tables it writes; that a stock LevelDB does so too stays UNPINNED.
+ *
+ * *d_table is always written.  The statuses are bits; on any of them no byte
+ * of d_handles is written.  In the order they are decided:
+ *   UPSTREAM     *d_upstream_status != 0.  Every other field is 0.
+ *   (empty)      file_bytes == 0 with no upstream status is the empty table
+ *                (upstream never writes one; lv_sst_build_device reports it as
+ *                file_bytes = 0): status 0, every field 0, nothing written,
+ *                and every get answers ABSENT.
+ *   NOT_A_TABLE  file_bytes < 48, file_bytes > file_cap, or the last 8 bytes
+ *                are not the magic.  file_bytes is reported from here on.
+ *   BAD_FOOTER   the footer's two handles, decoded by the rules of
+ *                lv_sst_footer_decode over its 48 bytes: a bad varint, or a
+ *                handle with offset + size + 5 > file_bytes (u64, no wrap) or
+ *                size >= 2^32 - 1.  The four handle fields are reported from
+ *                here on.
+ *   BAD_INDEX    the index block's type byte is not 0; its size is below 4;
+ *                n = LE32 of its last four bytes is not in
+ *                [1, (size - 4) / 4] (data_blocks = n from here on; arr =
+ *                size - 4 - 4 n); or some restart i does not hold entries that
+ *                decode: its run is [restart[i], restart[i + 1]), or
+ *                [restart[i], arr) for the last, which must be non-empty and
+ *                end at or below arr; its entries (decode, below, with the
+ *                run's end as the limit) must tile it exactly, the first with
+ *                shared == 0 and every other with shared <= the previous key's
+ *                length; every key must be at least 8 bytes; every value must
+ *                begin with two varint64s (lv_sst_block_handle_decode; trailing
+ *                bytes are ignored) that name a block in range by the footer's
+ *                rule.  A failing restart is not walked further.
+ *   INDEX_SHAPE  some restart run decodes but holds more than one entry.
+ *                Upstream's TableBuilder writes the index with restart
+ *                interval 1, as this project does; other shapes are
+ *                unsupported, not corrupt.
+ *   HANDLE_OVER  d_handles != NULL and data_blocks > block_cap; the true count
+ *                is reported.
+ * Every restart is judged whatever the others gave, so the status is the OR
+ * over all of them and does not depend on a search path.  On status 0
+ * d_handles receives the data_blocks data handles in index order, then the
+ * metaindex handle, then the index handle: data_blocks + 2 pairs in the layout
+ * lv_sst_build_device writes, so lv_sst_verify_blocks_device takes them
+ * unchanged (verify_checksums for an image whose handles the caller does not
+ * hold).  The caller provides room for block_cap + 2 pairs.
+ *
+ * Arguments, checked on the host before any device call (LV_ERR_INVALID,
+ * lv_last_error): NULL d_table or d_file_bytes, NULL d_file with file_cap != 0,
+ * NULL d_handles with block_cap != 0; d_table, d_file_bytes, d_upstream_status
+ * and d_handles 8-byte aligned; flags == 0; block_cap <= 2^32 - 4;
+ * d_handles[0, 2 (block_cap + 2)) must not overlap d_file[0, file_cap).
+ * Without a usable GPU a well-formed call fails with the runtime's error.
+ *
+ * Stream-ordered, no workspace, no host synchronisation.  A linear chain whose
+ * shape depends only on host values: a one-thread kernel (the footer and the
+ * index header); a validate kernel, one lane per index restart in a
+ * grid-stride loop over a grid sized from block_cap (from file_cap / 4096
+ * when block_cap is 0) and capped, which ORs its bits into d_table->status;
+ * and, with d_handles != NULL, an emit kernel that decodes the handles again
+ * and writes them when the status is 0.  Capturable into a HIP graph once the
+ * device has been initialised. */
+typedef struct lv_sst_table {            /* device memory, 8-B aligned, always written */
+    uint64_t file_bytes, metaindex_offset, metaindex_size, index_offset, index_size,
+             data_blocks, reserved, status;
+} lv_sst_table;
+#define LV_SST_OPEN_UPSTREAM     1u
+#define LV_SST_OPEN_NOT_A_TABLE  2u
+#define LV_SST_OPEN_BAD_FOOTER   4u
+#define LV_SST_OPEN_BAD_INDEX    8u
+#define LV_SST_OPEN_INDEX_SHAPE 16u
+#define LV_SST_OPEN_HANDLE_OVER 32u
+int lv_sst_open_device(const uint8_t *d_file, uint64_t file_cap,
+                       const uint64_t *d_file_bytes, const uint64_t *d_upstream_status,
+                       uint64_t *d_handles, size_t block_cap,
+                       lv_sst_table *d_table, uint32_t flags, void *stream);
+/* The host twin (pure, no GPU) over file[0, file_bytes): the same statuses but
+ * UPSTREAM.  Returns 0, or LV_ERR_INVALID for a NULL table, a NULL file with
+ * file_bytes != 0 or NULL handles with block_cap != 0. */
+int lv_sst_open_host(const uint8_t *file, uint64_t file_bytes, uint64_t *handles, size_t block_cap,
+                     lv_sst_table *table);
+
+/* ---- Get: Table::InternalGet + SaveValue for nq queries ---------------------
+ *
+ * Query q is the user key d_qkeys[d_q_off[q], d_q_off[q] + d_q_len[q]) at the
+ * snapshot d_q_seq[q]; the query arrays, the BAD_SEQ / BAD_QUERY rules and the
+ * status numbers 0-5 are lv_memtable_get_device's (memtable.h), so a caller
+ * falls through from memtable to table with one switch.  NO_TABLE: the open's
+ * status is not 0 (or d_table->file_bytes > file_cap: not this file's table).
+ * Checked in the order NO_TABLE, BAD_SEQ, BAD_QUERY.  Every field of every
+ * result is written; those a status does not set are 0 (CORRUPT and ABSENT
+ * set none).  file_bytes and the index handle come from *d_table on the
+ * device.  Get never reads outside d_file[0, file_bytes), even when given a
+ * d_table that open did not write for this file.
+ *
+ * The target is (user key, (seq << 8) | 1) under InternalKeyComparator: user
+ * key bytewise ascending, then tag descending.  The contract is this serial
+ * algorithm; for every image, corrupt ones included, the device returns what
+ * it returns.
+ *
+ *   Index seek.  file_bytes == 0: ABSENT.  The index handle is range-checked
+ *   again and the block's header read as in block_seek (CORRUPT).  lo = 0,
+ *   hi = n; while lo < hi: mid = lo + (hi - lo) / 2; decode the entry at
+ *   restart[mid] with limit arr (a failed decode, shared != 0 or a key shorter
+ *   than 8 bytes: CORRUPT); if its key is less than the target lo = mid + 1,
+ *   otherwise hi = mid.  lo == n: ABSENT.  Otherwise block = lo; its entry is
+ *   decoded again, its value must begin with a handle that is in range
+ *   (CORRUPT).
+ *   Data block.  A type byte at offset + size other than 0: CORRUPT
+ *   (compression is unsupported).  The checksum is not verified here: that is
+ *   lv_sst_verify_blocks_device over the open's handles.
+ *   block_seek(raw, size, target).  size < 4: corrupt.  n = LE32(raw[size-4:]);
+ *   n > (size - 4) / 4: corrupt; n == 0: no entry; arr = size - 4 - 4 n.
+ *   left = 0, right = n - 1; while left < right: mid = (left + right + 1) / 2;
+ *   decode at restart[mid] with limit arr (a failed decode, shared != 0 or a
+ *   key shorter than 8 bytes: corrupt); key < target: left = mid, otherwise
+ *   right = mid - 1.  Then at = restart[left], previous key length 0; loop:
+ *   at >= arr: no entry; decode at `at` (a failed decode, shared > the previous
+ *   key's length or a resulting key shorter than 8 bytes: corrupt); key not
+ *   less than the target: this entry; otherwise at = the end of its value.
+ *   decode(p, limit).  Fewer than 3 bytes before limit fails.  Three varint32
+ *   (shared, non_shared, value_len) by GetVarint32Ptr's rule: at most 5 bytes
+ *   each, none at or beyond limit, the fifth byte's bits beyond 2^32 dropped, a
+ *   sixth continuation byte fails.  limit - p < non_shared + value_len (u64)
+ *   fails.
+ *   SaveValue.  No entry: ABSENT (upstream does not step into the next block:
+ *   a shortened separator's user key is in no block).  The entry's user key
+ *   differs from the query's: ABSENT.  Otherwise its type byte 1: FOUND with
+ *   val_off (absolute in d_file), val_len, tag, block; 0: DELETED with tag,
+ *   block; any other: CORRUPT.
+ *
+ * Keys may have any length: no key is materialised and no buffer scales with
+ * the table's key lengths (csrc/lvk/sst_read.h keeps four registers per lane).
+ *
+ * One launch, one lane per query, its shape depending only on nq;
+ * stream-ordered, no host synchronisation, capturable like the open.
+ * Arguments checked on the host (LV_ERR_INVALID): NULL d_table, NULL d_file
+ * with file_cap != 0, NULL d_qkeys with qkeys_bytes != 0, NULL query arrays or
+ * d_results with nq != 0; d_table, d_q_off, d_q_seq and d_results 8-byte
+ * aligned, d_q_len 4-byte aligned; flags == 0; nq <= 2^32 - 2;
+ * d_results[0, nq) must not overlap d_file[0, file_cap). */
+#define LV_SST_GET_ABSENT    0u
+#define LV_SST_GET_FOUND     1u
+#define LV_SST_GET_DELETED   2u
+#define LV_SST_GET_BAD_SEQ   3u
+#define LV_SST_GET_NO_TABLE  4u
+#define LV_SST_GET_BAD_QUERY 5u
+#define LV_SST_GET_CORRUPT   6u
+typedef struct lv_sst_get_result {       /* 32 bytes */
+    uint64_t val_off;                    /* absolute offset of the value in d_file */
+    uint64_t tag;                        /* (sequence << 8) | type of the entry answered */
+    uint32_t val_len, block, status, reserved;
+} lv_sst_get_result;
+int lv_sst_get_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_table *d_table,
+                      const uint8_t *d_qkeys, size_t qkeys_bytes, const uint64_t *d_q_off,
+                      const uint32_t *d_q_len, const uint64_t *d_q_seq, size_t nq,
+                      lv_sst_get_result *d_results, uint32_t flags, void *stream);
+/* The host twin (pure, no GPU) for one query over file[0, table->file_bytes):
+ * the same algorithm compiled for the host.  Returns 0, or LV_ERR_INVALID for
+ * a NULL table or result, a NULL file with table->file_bytes != 0 or a NULL
+ * qkey with qkey_len != 0 (or qkey_len >= 2^32). */
+int lv_sst_get_host(const uint8_t *file, const lv_sst_table *table, const uint8_t *qkey, size_t qkey_len,
+                    uint64_t seq, lv_sst_get_result *result);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,13 @@ block-trailer seal/verify and the SSTable build over include/lvgpu/table.h.
     build_device(table)               lv_sst_build_device over a
                                       lvgpu.memtable.Table; no host sync until
                                       .sync_totals() / .file() / .handles()
+    open_host(file)                   lv_sst_open_host: (table dict, handles)
+    get_host(file, table, key, seq)   lv_sst_get_host: a result dict
+    open_device(file_t, file_bytes)   lv_sst_open_device: an Opened (the table and
+                                      the handles in HBM), asynchronous
+    get_device(opened, qkeys, q_off, q_len, q_seq)
+                                      lv_sst_get_device: a Gets, asynchronous until
+                                      .sync()
 """
 from __future__ import annotations
 
@@ -335,3 +342,220 @@ def build_device(table, *, block_size=None, restart_interval=None, file_cap=None
     if rc != 0:
         raise LvError(f"lv_sst_build_device: {lib().lv_last_error().decode()}")
     return Built(file_t, file_cap, handles_t, block_cap, totals, (table, workspace))
+
+
+# ---- lv_sst_open_* / lv_sst_get_*: Table::Open and Table::InternalGet ----------
+OPEN_STATUS = {1: "UPSTREAM", 2: "NOT_A_TABLE", 4: "BAD_FOOTER", 8: "BAD_INDEX", 16: "INDEX_SHAPE",
+               32: "HANDLE_OVER"}  # LV_SST_OPEN_*
+OPEN_UPSTREAM, OPEN_NOT_A_TABLE, OPEN_BAD_FOOTER, OPEN_BAD_INDEX, OPEN_INDEX_SHAPE, OPEN_HANDLE_OVER = OPEN_STATUS
+(GET_ABSENT, GET_FOUND, GET_DELETED, GET_BAD_SEQ, GET_NO_TABLE, GET_BAD_QUERY, GET_CORRUPT) = range(7)  # LV_SST_GET_*
+TABLE_FIELDS = ("file_bytes", "metaindex_offset", "metaindex_size", "index_offset", "index_size", "data_blocks",
+                "reserved", "status")
+GET_DTYPE = np.dtype([("val_off", "<u8"), ("tag", "<u8"), ("val_len", "<u4"), ("block", "<u4"), ("status", "<u4"),
+                      ("reserved", "<u4")])
+assert GET_DTYPE.itemsize == 32
+HANDLE_CANARY = 0xA5A5A5A5A5A5A5A5
+
+
+class SstTable(ctypes.Structure):
+    """lv_sst_table."""
+    _fields_ = [(n, ctypes.c_uint64) for n in TABLE_FIELDS]
+
+
+class SstGetResult(ctypes.Structure):
+    """lv_sst_get_result."""
+    _fields_ = [("val_off", ctypes.c_uint64), ("tag", ctypes.c_uint64), ("val_len", ctypes.c_uint32),
+                ("block", ctypes.c_uint32), ("status", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+_get_bound = False
+
+
+def _bind_get():
+    global _get_bound
+    L = _bind()
+    if not _get_bound:
+        vp, sz, u64, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32
+        L.lv_sst_open_host.restype = ctypes.c_int
+        L.lv_sst_open_host.argtypes = [vp, u64, vp, sz, vp]
+        L.lv_sst_get_host.restype = ctypes.c_int
+        L.lv_sst_get_host.argtypes = [vp, vp, vp, sz, u64, vp]
+        L.lv_sst_open_device.restype = ctypes.c_int
+        L.lv_sst_open_device.argtypes = [vp, u64, vp, vp, vp, sz, vp, u32, vp]
+        L.lv_sst_get_device.restype = ctypes.c_int
+        L.lv_sst_get_device.argtypes = [vp, u64, vp, vp, sz, vp, vp, vp, sz, vp, u32, vp]
+        _get_bound = True
+    return L
+
+
+def _status_names(st):
+    return "|".join(n for b, n in OPEN_STATUS.items() if st & b)
+
+
+def open_host(file, *, block_cap=None, handles=True):
+    """lv_sst_open_host over the bytes `file`: (table dict, handles).  With
+    status 0 the handles are the data_blocks + 2 (offset, size) pairs; with a
+    status they are the canary-filled uint64 array the call was given, for the
+    caller to check.  block_cap defaults to the table's data_blocks (a first
+    call without handles reads it); handles=False passes NULL and block_cap 0."""
+    L = _bind_get()
+    fb = bytes(file)
+    t = SstTable()
+
+    def call(hp, bc):
+        rc = L.lv_sst_open_host(fb, len(fb), hp, bc, ctypes.byref(t))
+        if rc != 0:
+            raise LvError(f"lv_sst_open_host: {rc}")
+        return {n: int(getattr(t, n)) for n in TABLE_FIELDS}
+
+    if not handles:
+        return call(None, 0), []
+    if block_cap is None:
+        block_cap = call(None, 0)["data_blocks"]
+    hs = np.full(2 * (block_cap + 2) + 8, HANDLE_CANARY, dtype=np.uint64)
+    tab = call(hs.ctypes.data, block_cap)
+    if tab["status"]:
+        return tab, hs
+    nh = tab["data_blocks"] + 2 if tab["file_bytes"] else 0
+    assert (hs[2 * nh:] == HANDLE_CANARY).all(), "lv_sst_open_host wrote handles beyond its count"
+    return tab, [(int(hs[2 * i]), int(hs[2 * i + 1])) for i in range(nh)]
+
+
+def get_host(file, table, key, seq) -> dict:
+    """lv_sst_get_host for one query over the bytes `file` and the table dict
+    of open_host: a dict of the result's fields."""
+    L = _bind_get()
+    t = SstTable(*[int(table[n]) for n in TABLE_FIELDS])
+    r = SstGetResult()
+    kb = bytes(key)
+    rc = L.lv_sst_get_host(file if isinstance(file, bytes) else bytes(file), ctypes.byref(t), kb, len(kb), seq,
+                           ctypes.byref(r))
+    if rc != 0:
+        raise LvError(f"lv_sst_get_host: {rc}")
+    return {n: int(getattr(r, n)) for n, _ in SstGetResult._fields_}
+
+
+class Opened:
+    """Outputs of open_device, CUDA tensors written asynchronously: table
+    (int64[8], TABLE_FIELDS) and handles_t (int64, block_cap + 2 pairs and the
+    guard, or None), with the image a get needs."""
+
+    def __init__(self, file_t, file_cap, table, handles_t, block_cap, keep):
+        self.file_t, self.file_cap, self.table, self.handles_t, self.block_cap = file_t, file_cap, table, handles_t, block_cap
+        self._keep = keep
+        self._tab = None
+
+    def sync(self, check: bool = True) -> dict:
+        """Waits for the call; the table as a dict.  Raises LvError naming the
+        status bits if one is set unless check is False."""
+        if self._tab is None:
+            _torch().cuda.synchronize(self.table.device)
+            self._tab = dict(zip(TABLE_FIELDS, (int(v) for v in self.table.cpu().numpy().view(np.uint64))))
+            self._keep = None
+        st = self._tab["status"]
+        if st and check:
+            raise LvError(f"lv_sst_open_device: status {_status_names(st)} (table {self._tab})")
+        return self._tab
+
+    def handles(self) -> list:
+        """The data_blocks + 2 handles as (offset, size) pairs (synchronises)."""
+        t = self.sync()
+        n = t["data_blocks"] + 2 if t["file_bytes"] else 0
+        h = self.handles_t[: 2 * n].cpu().numpy().view(np.uint64)
+        return [(int(h[2 * i]), int(h[2 * i + 1])) for i in range(n)]
+
+    def handles_view(self):
+        """The written handles as an (n, 2) int64 CUDA tensor for verify_blocks
+        (synchronises for the count)."""
+        t = self.sync()
+        n = t["data_blocks"] + 2 if t["file_bytes"] else 0
+        return self.handles_t[: 2 * n].view(n, 2)
+
+
+def open_device(file_t, file_bytes, upstream_status=None, *, file_cap=None, block_cap=0, handles=True, table=None,
+                handles_t=None, stream=None, fill=None, guard: int = 0, flags: int = 0):
+    """lv_sst_open_device.  file_t is a uint8 CUDA tensor (any byte alignment:
+    a slice will do) that holds the image; file_bytes and upstream_status are
+    int64 CUDA tensors whose first element is read on the device (e.g.
+    Built.totals[2:3] and Built.totals[7:8]).  file_cap defaults to
+    file_t.numel().  handles=False passes a NULL d_handles.  table / handles_t
+    reuse the outputs of an earlier call (graph replays).  fill / guard as in
+    build_device.  Returns an Opened; asynchronous on `stream`."""
+    torch = _torch()
+    L = _bind_get()
+    dev = file_t.device
+    if file_t.dtype != torch.uint8:
+        raise LvError("file_t must be a uint8 tensor")
+    for name, t in (("file_bytes", file_bytes), ("upstream_status", upstream_status)):
+        if t is None and name == "upstream_status":
+            continue
+        if t is None or t.dtype != torch.int64 or t.device != dev or t.numel() < 1:
+            raise LvError(f"{name} must be an int64 tensor on the file's device")
+    file_cap = file_t.numel() if file_cap is None else int(file_cap)
+    if handles and handles_t is None:
+        hbytes = (16 * (block_cap + 2) + guard + 7) & ~7
+        if fill is None:
+            handles_t = torch.empty(hbytes, dtype=torch.uint8, device=dev).view(torch.int64)
+        else:
+            handles_t = torch.full((hbytes,), fill, dtype=torch.uint8, device=dev).view(torch.int64)
+    if not handles:
+        handles_t = None
+    if table is None:
+        table = torch.empty(len(TABLE_FIELDS), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):  # the C call runs on the current device
+        rc = L.lv_sst_open_device(_dev_ptr(file_t, "file") if file_cap else None, file_cap,
+                                  _dev_ptr(file_bytes, "file_bytes"), _dev_ptr(upstream_status, "upstream_status"),
+                                  _dev_ptr(handles_t, "handles"), block_cap, _dev_ptr(table, "table"), flags,
+                                  _stream_ptr(stream))
+    if rc != 0:
+        raise LvError(f"lv_sst_open_device: {lib().lv_last_error().decode()}")
+    return Opened(file_t, file_cap, table, handles_t, block_cap, (file_bytes, upstream_status))
+
+
+class Gets:
+    """Output of get_device: res, a uint8 CUDA tensor of nq lv_sst_get_result
+    (and the guard), written asynchronously."""
+
+    def __init__(self, res, nq, keep):
+        self.res, self.nq = res, nq
+        self._keep = keep  # the query arrays, until the work has run
+        self._out = None
+
+    def sync(self):
+        """Waits for the call; the results as a structured array (GET_DTYPE)."""
+        if self._out is None:
+            _torch().cuda.synchronize(self.res.device)
+            self._out = self.res[: self.nq * 32].cpu().numpy().view(GET_DTYPE).copy()
+            self._keep = None
+        return self._out
+
+
+def get_device(opened, qkeys, q_off, q_len, q_seq, *, nq=None, res=None, stream=None, fill=None, guard: int = 0,
+               flags: int = 0):
+    """lv_sst_get_device over an Opened (its image and its table, read on the
+    device).  qkeys is a uint8 CUDA tensor, q_off / q_seq int64 and q_len int32
+    CUDA tensors of nq entries.  res reuses an earlier call's tensor.  Returns
+    a Gets; asynchronous on `stream`."""
+    torch = _torch()
+    L = _bind_get()
+    dev = opened.file_t.device
+    if qkeys.dtype != torch.uint8 or q_off.dtype != torch.int64 or q_seq.dtype != torch.int64 or \
+            q_len.dtype != torch.int32:
+        raise LvError("qkeys must be uint8, q_off and q_seq int64, q_len int32")
+    nq = int(min(q_off.numel(), q_len.numel(), q_seq.numel())) if nq is None else int(nq)
+    if min(q_off.numel(), q_len.numel(), q_seq.numel()) < nq:
+        raise LvError("the query arrays must hold nq entries")
+    if res is None:
+        nbytes = (max(nq * 32, 16) + guard + 7) & ~7
+        if fill is None:
+            res = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        else:
+            res = torch.full((nbytes,), fill, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.lv_sst_get_device(_dev_ptr(opened.file_t, "file") if opened.file_cap else None, opened.file_cap,
+                                 _dev_ptr(opened.table, "table"), _dev_ptr(qkeys, "qkeys") if qkeys.numel() else None,
+                                 qkeys.numel(), _dev_ptr(q_off, "q_off"), _dev_ptr(q_len, "q_len"),
+                                 _dev_ptr(q_seq, "q_seq"), nq, _dev_ptr(res, "results"), flags, _stream_ptr(stream))
+    if rc != 0:
+        raise LvError(f"lv_sst_get_device: {lib().lv_last_error().decode()}")
+    return Gets(res, nq, (opened, qkeys, q_off, q_len, q_seq))
