@@ -405,6 +405,143 @@ int lv_sst_get_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_tab
 int lv_sst_get_host(const uint8_t *file, const lv_sst_table *table, const uint8_t *qkey, size_t qkey_len,
                     uint64_t seq, lv_sst_get_result *result);
 
+/* ---- Scan: Table::NewIterator walked to the end, every entry at once --------
+ *
+ * A table image back to an op table.  lv_sst_scan_device decodes every entry
+ * of the image d_file[0, d_table->file_bytes) that lv_sst_open_device opened
+ * (*d_table is read on the device in stream order): prefix-compressed keys are
+ * materialised, values copied, one lv_wb_op written per entry.  The result is
+ * what lv_memtable_build_device and lv_sst_build_device read, so a table can
+ * be rewritten with other options, and several tables can be scanned into one
+ * arena, sorted by the memtable build and flushed by the table build: a major
+ * compaction that drops nothing.  The merging iterator as a streaming object,
+ * dropping shadowed entries, several output files and version edits are not
+ * part of this.  d_file may have any byte alignment.
+ *
+ * Output.  base_e / base_b are d_prev->entries / d_prev->arena_bytes, or 0
+ * with a NULL d_prev.  Entry i of the table, in table order (index order, then
+ * block order), becomes d_ops[base_e + i]: tag is the last 8 bytes of its
+ * internal key, little-endian, whatever the type byte (an iterator passes
+ * tags through); its user key is materialised at d_arena[key_off, key_off +
+ * key_len) and its value copied directly behind, val_off = key_off + key_len
+ * always (lv_wb_op's DELETION convention too).  Entries are packed without
+ * gaps from base_b on; offsets are relative to d_arena, which may have any
+ * byte alignment.  So table_bytes = sum(key_len + val_len) and there is one
+ * correct arena, byte for byte.  For a table lv_sst_build_device wrote,
+ * table_bytes is the sum of the source ops' key and value lengths; for a
+ * foreign image one retry after ARENA_OVER sizes the arena.
+ *
+ * d_order and d_mt_totals are both NULL or both not; with them d_prev must be
+ * NULL.  They complete a memtable quadruple (d_arena as d_payload, d_ops,
+ * d_order, *d_mt_totals) that lv_sst_build_device and lv_memtable_get_device
+ * take as it is: d_order[i] = i, entries = table_entries, user_keys counted as
+ * the memtable build counts it, status 0 when no entry comes before its
+ * predecessor under lv_internal_key_compare (equal is allowed: exact
+ * duplicates), otherwise status = LV_SST_SCAN_MT_UNORDERED and user_keys = 0;
+ * both consumers refuse a status.  On any scan status *d_mt_totals is
+ * {0, 0, LV_MT_BUILD_UPSTREAM} and d_order is not written.
+ *
+ * Appending.  With d_prev a table's entries go behind those of the scan that
+ * wrote *d_prev (read on the device; d_prev == d_totals is LV_ERR_INVALID) in
+ * the same arena and op table; entries and arena_bytes are cumulative.
+ * &d_totals->entries and &d_totals->status of the last scan are then
+ * lv_memtable_build_device's d_n_ops and d_upstream_status.
+ *
+ * *d_totals is always written.  The statuses are bits, decided once, before
+ * any byte of d_arena, d_ops or d_order is written; on any of them none of the
+ * three is written.
+ *   UPSTREAM    d_prev->status != 0.
+ *   NO_TABLE    d_table->status != 0, or d_table->file_bytes > file_cap.
+ *               With either of these two nothing of the image is read.
+ *   CORRUPT     the serial algorithm below says so.
+ *   BLOCK_OVER  the index names more data blocks than block_cap; the true
+ *               data_blocks is reported and no index entry or block is read.
+ *   With any of these four table_entries = table_bytes = runs = 0, entries =
+ *   base_e and arena_bytes = base_b.
+ *   OP_OVER     base_e + table_entries > op_cap.
+ *   ARENA_OVER  base_b + table_bytes > arena_cap.
+ *   With only these two every count is the true one, so one retry suffices.
+ * file_bytes == 0 with status 0 is the empty table: no entries, status 0.
+ * data_blocks is the index block's restart count once its header is sound;
+ * runs is the number of restart runs of all data blocks.
+ *
+ * The contract for bytes is this serial algorithm; the scan never reads
+ * outside d_file[0, file_bytes), even when given a d_table that open did not
+ * write for this file.  decode, the restart-array header (n, arr) and the
+ * handle's range rule are Get's (above).
+ *   Index.  The index handle of *d_table is range-checked again; its type
+ *   byte must be 0 and its header is read as in Get; n must equal
+ *   d_table->data_blocks (CORRUPT).  For restart i in order: decode at
+ *   restart[i] with limit arr; a failed decode, shared != 0, a key under 8
+ *   bytes, a value that does not begin with a handle, a handle out of range
+ *   or a data block whose type byte is not 0: CORRUPT.  (Open has walked the
+ *   runs of the index; the scan reads each restart's first entry, as Get.)
+ *   Data block.  A header that does not decode: CORRUPT.  n == 0: no entries
+ *   and no run.  n == 1 and arr == 0: one run, no entries (the empty
+ *   BlockBuilder).  Otherwise restart[0] == 0, the restarts strictly increase
+ *   and the last is below arr.  Run r is [restart[r], restart[r + 1]), or ends
+ *   at arr for the last; its entries, decoded with the run's end as the limit,
+ *   must tile it exactly; the first has shared == 0, every other shared <= the
+ *   previous key's length; every key is at least 8 bytes.  Any violation:
+ *   CORRUPT.
+ * This is stricter than upstream's Block::Iter, which never looks at the
+ * restart array while it steps; every block a BlockBuilder writes passes.  It
+ * is also what makes the runs independent of each other, so that each can be
+ * given to a lane.  The checksums are not verified here: that is
+ * lv_sst_verify_blocks_device over the open's handles.
+ *
+ * Arguments, checked on the host before any device call (LV_ERR_INVALID,
+ * lv_last_error): NULL pointers (d_file only with file_cap == 0, d_arena only
+ * with arena_cap == 0, d_ops only with op_cap == 0; d_prev may be NULL), d_ops
+ * 16-byte aligned, d_table, d_prev, d_totals and d_mt_totals 8-byte aligned,
+ * d_order 4-byte aligned, d_workspace 16-byte aligned and >=
+ * lv_sst_scan_workspace_bytes(op_cap, block_cap) bytes, flags == 0, op_cap <=
+ * 2^32 - 2, block_cap <= 2^32 - 4, the pairing rules of d_order, d_mt_totals
+ * and d_prev, and d_arena[0, arena_cap), d_ops[0, op_cap) and d_order[0,
+ * op_cap) must overlap neither d_file[0, file_cap) nor each other.  Without a
+ * usable GPU a well-formed call fails with the runtime's error.
+ *
+ * Stream-ordered, no host synchronisation.  The launch sequence depends only
+ * on op_cap, block_cap and whether d_order is NULL: a one-thread header (it
+ * zeroes the call's state in the workspace); with block_cap != 0 a lane per
+ * data block (handle, header, run count, with a tile scan and its carries),
+ * then a lane per run that walks it keeping lengths (two tile scans with their
+ * carries; the workspace holds op_cap + block_cap runs, and a table with more
+ * is OP_OVER, whose true counts are atomic sums); the one-thread plan, which
+ * decides every status; with op_cap and block_cap != 0 the emit, a lane per
+ * run; with d_order the order kernel and a one-thread finish.  No workgroup
+ * waits on another.  Capturable into a HIP graph once the device has been
+ * initialised. */
+typedef struct lv_sst_scan_totals {      /* device memory, 8-B aligned, always written */
+    uint64_t entries, arena_bytes,       /* cumulative: d_prev's plus this table's */
+             table_entries, table_bytes, /* this table's alone */
+             data_blocks, runs, reserved, status;
+} lv_sst_scan_totals;
+#define LV_SST_SCAN_UPSTREAM    1u
+#define LV_SST_SCAN_NO_TABLE    2u
+#define LV_SST_SCAN_CORRUPT     4u
+#define LV_SST_SCAN_BLOCK_OVER  8u
+#define LV_SST_SCAN_OP_OVER    16u
+#define LV_SST_SCAN_ARENA_OVER 32u
+#define LV_SST_SCAN_MT_UNORDERED 8u      /* a bit of d_mt_totals->status only; distinct from LV_MT_BUILD_* */
+
+size_t lv_sst_scan_workspace_bytes(size_t op_cap, size_t block_cap);
+int lv_sst_scan_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_table *d_table,
+                       const lv_sst_scan_totals *d_prev,
+                       uint8_t *d_arena, uint64_t arena_cap, lv_wb_op *d_ops, size_t op_cap, size_t block_cap,
+                       uint32_t *d_order, lv_mt_totals *d_mt_totals,
+                       lv_sst_scan_totals *d_totals, uint32_t flags,
+                       void *d_workspace, size_t workspace_bytes, void *stream);
+/* The host twin (pure, no GPU) over file[0, table->file_bytes): the same
+ * algorithm compiled for the host, with the same statuses but BLOCK_OVER
+ * (and NO_TABLE only from table->status).  Returns 0, or LV_ERR_INVALID for a
+ * NULL table or totals, prev == totals, a NULL file, arena or ops the call
+ * needs, order and mt_totals not paired or given with prev, or op_cap above
+ * 2^32 - 2. */
+int lv_sst_scan_host(const uint8_t *file, const lv_sst_table *table, const lv_sst_scan_totals *prev,
+                     uint8_t *arena, uint64_t arena_cap, lv_wb_op *ops, size_t op_cap,
+                     uint32_t *order, lv_mt_totals *mt_totals, lv_sst_scan_totals *totals);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,10 @@
     defined(LVK_MT_PREFIX) || \
     defined(LVK_SB_TILE) || \
     defined(LVK_SB_WAVE_COPY) || \
-    defined(LVK_SB_COPY_LANES))
+    defined(LVK_SB_COPY_LANES) || \
+    defined(LVK_SS_TILE) || \
+    defined(LVK_SS_WAVE_COPY) || \
+    defined(LVK_SS_COPY_LANES))
 #error "LVK_* kernel switches select untested code paths; only experiment variants (LVK_EXPERIMENT_BUILD, tools/build_variant.sh) may set them"
 #endif
 
@@ -104,4 +107,13 @@
 #endif
 #ifndef LVK_SB_COPY_LANES  // SSTable build: lanes of a wave that share one such copy (16, 32 or 64; 64 / this many copies run at a time)
 #define LVK_SB_COPY_LANES 16
+#endif
+#ifndef LVK_SS_TILE  // SSTable scan: blocks, and restart runs, per scan tile; a multiple of 256
+#define LVK_SS_TILE 1024
+#endif
+#ifndef LVK_SS_WAVE_COPY  // SSTable scan: a key prefix, key suffix or value of at least this many bytes is copied by its wave, not its lane (>= 16)
+#define LVK_SS_WAVE_COPY 64
+#endif
+#ifndef LVK_SS_COPY_LANES  // SSTable scan: lanes of a wave that share one such copy, a power of two <= 64 (r12, 100-byte values: 4 is 9 % faster than 16 on a 61 MB image and 1 % slower on a 244 MB one, 2 and 8 lie between; 32 and 64 are 22 % and 55 % slower)
+#define LVK_SS_COPY_LANES 4
 #endif

@@ -16,6 +16,14 @@ block-trailer seal/verify and the SSTable build over include/lvgpu/table.h.
     get_device(opened, qkeys, q_off, q_len, q_seq)
                                       lv_sst_get_device: a Gets, asynchronous until
                                       .sync()
+    scan_host(file, table, prev)      lv_sst_scan_host: (totals dict, ops, arena,
+                                      memtable totals)
+    scan_workspace_bytes(op_cap, block_cap)
+                                      device workspace of scan_device
+    scan_device(opened, prev)         lv_sst_scan_device: a Scanned (ops, arena,
+                                      totals; .memtable() is what build_device and
+                                      lvgpu.memtable.get_device take), asynchronous
+                                      until .sync()
 """
 from __future__ import annotations
 
@@ -559,3 +567,195 @@ def get_device(opened, qkeys, q_off, q_len, q_seq, *, nq=None, res=None, stream=
     if rc != 0:
         raise LvError(f"lv_sst_get_device: {lib().lv_last_error().decode()}")
     return Gets(res, nq, (opened, qkeys, q_off, q_len, q_seq))
+
+
+# ---- lv_sst_scan_*: a table image back to a sorted op table --------------------
+SCAN_STATUS = {1: "UPSTREAM", 2: "NO_TABLE", 4: "CORRUPT", 8: "BLOCK_OVER", 16: "OP_OVER",
+               32: "ARENA_OVER"}  # LV_SST_SCAN_*
+SCAN_UPSTREAM, SCAN_NO_TABLE, SCAN_CORRUPT, SCAN_BLOCK_OVER, SCAN_OP_OVER, SCAN_ARENA_OVER = SCAN_STATUS
+SCAN_MT_UNORDERED = 8  # a bit of the memtable totals' status only
+SCAN_TOTALS = ("entries", "arena_bytes", "table_entries", "table_bytes", "data_blocks", "runs", "reserved", "status")
+# csrc/lvk/knobs.h: LVK_SS_TILE (blocks, and restart runs, per scan tile) and
+# LVK_SS_WAVE_COPY (a key prefix, key suffix or value of at least this many
+# bytes is copied by its wave, not its lane).  The GPU tests sweep around both.
+SS_TILE = 1024
+SS_WAVE_COPY = 64
+
+
+class ScanTotals(ctypes.Structure):
+    """lv_sst_scan_totals."""
+    _fields_ = [(n, ctypes.c_uint64) for n in SCAN_TOTALS]
+
+
+_scan_bound = False
+
+
+def _bind_scan():
+    global _scan_bound
+    L = _bind_get()
+    if not _scan_bound:
+        vp, sz, u64, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32
+        L.lv_sst_scan_workspace_bytes.restype = sz
+        L.lv_sst_scan_workspace_bytes.argtypes = [sz, sz]
+        L.lv_sst_scan_device.restype = ctypes.c_int
+        L.lv_sst_scan_device.argtypes = [vp, u64, vp, vp, vp, u64, vp, sz, sz, vp, vp, vp, u32, vp, sz, vp]
+        L.lv_sst_scan_host.restype = ctypes.c_int
+        L.lv_sst_scan_host.argtypes = [vp, vp, vp, vp, u64, vp, sz, vp, vp, vp]
+        _scan_bound = True
+    return L
+
+
+def scan_workspace_bytes(op_cap: int, block_cap: int) -> int:
+    return int(_bind_scan().lv_sst_scan_workspace_bytes(op_cap, block_cap))
+
+
+def scan_host(file, table, prev=None, *, arena=None, ops=None, arena_cap=None, op_cap=None, order=False, fill=0xA5):
+    """lv_sst_scan_host over the bytes `file` and the table dict of open_host:
+    (totals dict, ops array, arena bytes, mt_totals dict or None).  prev is the
+    totals dict of the scan to append to, with `arena` (a uint8 array) and
+    `ops` that scan returned whole (see below).  arena_cap / op_cap default to
+    what a sizing call reports.  The arena and the ops come back whole, all
+    arena_cap bytes and op_cap ops, the part no entry was written to still
+    holding `fill`, for the caller to check or to append to; with order=True
+    the fourth value carries the order array under "order"."""
+    from .write_batch import OP_DTYPE
+    L = _bind_scan()
+    fb = bytes(file)
+    t = SstTable(*[int(table[n]) for n in TABLE_FIELDS])
+    pv = None if prev is None else ScanTotals(*[int(prev[n]) for n in SCAN_TOTALS])
+    tot = ScanTotals()
+
+    def call(ap, acap, opp, ocap, orp, mtp):
+        rc = L.lv_sst_scan_host(fb, ctypes.byref(t), ctypes.byref(pv) if pv else None, ap, acap, opp, ocap, orp, mtp,
+                                ctypes.byref(tot))
+        if rc != 0:
+            raise LvError(f"lv_sst_scan_host: {rc}")
+        return {n: int(getattr(tot, n)) for n in SCAN_TOTALS}
+
+    if arena_cap is None or op_cap is None:
+        sized = call(None, 0, None, 0, None, None)
+        arena_cap = sized["arena_bytes"] if arena_cap is None else arena_cap
+        op_cap = sized["entries"] if op_cap is None else op_cap
+    abuf = np.full(arena_cap, fill, dtype=np.uint8)
+    obuf = np.frombuffer(bytes([fill]) * (32 * op_cap), dtype=OP_DTYPE).copy()
+    if arena is not None:
+        n = min(len(arena), arena_cap)
+        abuf[:n] = np.frombuffer(bytes(arena), dtype=np.uint8)[:n]
+    if ops is not None:
+        n = min(len(ops), op_cap)
+        obuf[:n] = ops[:n]
+    orr = np.full(max(op_cap, 1), 0xA5A5A5A5, dtype=np.uint32) if order else None
+    mt = MtTotals() if order else None
+    tt = call(abuf.ctypes.data if arena_cap else None, arena_cap, obuf.ctypes.data if op_cap else None, op_cap,
+              orr.ctypes.data if order else None, ctypes.byref(mt) if order else None)
+    mtd = None
+    if order:
+        mtd = dict(entries=int(mt.entries), user_keys=int(mt.user_keys), status=int(mt.status), order=orr[:op_cap])
+    return tt, obuf, abuf, mtd
+
+
+class Scanned:
+    """Outputs of scan_device, CUDA tensors written asynchronously: arena_t
+    (uint8; the arena is arena_t[arena_shift:]), ops_t (uint8, 32 bytes per
+    lv_wb_op), totals (int64[8], SCAN_TOTALS) and, with order=True, order_t
+    (int32) and mt_totals (int64[3])."""
+
+    def __init__(self, arena_t, arena_cap, ops_t, op_cap, block_cap, totals, order_t, mt_totals, keep):
+        self.arena_t, self.arena_cap, self.ops_t, self.op_cap, self.block_cap = arena_t, arena_cap, ops_t, op_cap, block_cap
+        self.totals, self.order_t, self.mt_totals = totals, order_t, mt_totals
+        self._keep = keep
+        self._tot = None
+
+    def sync(self, check: bool = True) -> dict:
+        """Waits for the call; the totals as a dict.  Raises LvError naming the
+        status bits if one is set (nothing was written) unless check is False."""
+        if self._tot is None:
+            _torch().cuda.synchronize(self.totals.device)
+            self._tot = dict(zip(SCAN_TOTALS, (int(v) for v in self.totals.cpu().numpy().view(np.uint64))))
+            self._keep = None
+        st = self._tot["status"]
+        if st and check:
+            names = "|".join(n for b, n in SCAN_STATUS.items() if st & b)
+            raise LvError(f"lv_sst_scan_device: status {names} (totals {self._tot})")
+        return self._tot
+
+    def ops(self):
+        """d_ops[0, entries) as a structured array (synchronises)."""
+        from .write_batch import OP_DTYPE
+        n = self.sync()["entries"]
+        return self.ops_t[: 32 * n].cpu().numpy().view(OP_DTYPE).copy()
+
+    def arena(self) -> bytes:
+        """d_arena[0, arena_bytes) (synchronises)."""
+        n = self.sync()["arena_bytes"]
+        return self.arena_t[:n].cpu().numpy().tobytes()
+
+    def mt(self) -> dict:
+        """*d_mt_totals as a dict (synchronises)."""
+        self.sync(check=False)
+        return dict(zip(("entries", "user_keys", "status"), (int(v) for v in self.mt_totals.cpu().numpy().view(np.uint64))))
+
+    def memtable(self):
+        """The quadruple as a lvgpu.memtable.Table: what build_device here and
+        lvgpu.memtable.get_device take where they take a memtable build's
+        result.  Needs order=True; does not synchronise."""
+        from .memtable import Table
+        if self.order_t is None:
+            raise LvError("scan_device was called without order=True")
+        return Table(self.arena_t[: max(self.arena_cap, 0)], self.ops_t, self.op_cap, self.order_t, self.mt_totals, self)
+
+
+def scan_device(opened, prev=None, *, arena_cap=None, op_cap=None, block_cap=None, order=False, arena_t=None,
+                ops_t=None, order_t=None, mt_totals=None, totals=None, workspace=None, stream=None, fill=None,
+                guard: int = 0, flags: int = 0):
+    """lv_sst_scan_device over an Opened (its image and its table, read on the
+    device).  prev is the Scanned to append to: its arena and ops are reused
+    (with its caps) and its totals are d_prev.  arena_cap defaults to the
+    image's capacity (a table's keys and values are no longer than its file
+    only when keys share nothing; size by a retry on ARENA_OVER), op_cap to
+    file_cap // 11 + 1 (an entry with a tag takes at least 11 bytes), block_cap
+    to the Opened's, or file_cap // 13 + 1.  arena_t may be any uint8 CUDA
+    tensor (a slice: any alignment).  order=True also writes d_order and
+    d_mt_totals.  fill / guard as in build_device.  Returns a Scanned;
+    asynchronous on `stream`."""
+    torch = _torch()
+    L = _bind_scan()
+    dev = opened.file_t.device
+    if prev is not None:
+        arena_t, arena_cap, ops_t, op_cap = prev.arena_t, prev.arena_cap, prev.ops_t, prev.op_cap
+    if arena_cap is None:
+        arena_cap = int(opened.file_cap) if arena_t is None else arena_t.numel()
+    if op_cap is None:
+        op_cap = opened.file_cap // 11 + 1
+    if block_cap is None:
+        block_cap = opened.block_cap or opened.file_cap // 13 + 1
+
+    def alloc(nbytes, dtype=None):
+        nbytes = (max(nbytes, 16) + guard + 15) & ~15
+        t = (torch.empty(nbytes, dtype=torch.uint8, device=dev) if fill is None
+             else torch.full((nbytes,), fill, dtype=torch.uint8, device=dev))
+        return t if dtype is None else t.view(dtype)
+    if arena_t is None:
+        arena_t = alloc(arena_cap)
+    if ops_t is None:
+        ops_t = alloc(32 * op_cap)
+    if order and order_t is None:
+        order_t = alloc(4 * op_cap, torch.int32)
+    if order and mt_totals is None:
+        mt_totals = torch.empty(3, dtype=torch.int64, device=dev)
+    if totals is None:
+        totals = torch.empty(len(SCAN_TOTALS), dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(L.lv_sst_scan_workspace_bytes(op_cap, block_cap), 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.lv_sst_scan_device(_dev_ptr(opened.file_t, "file") if opened.file_cap else None, opened.file_cap,
+                                  _dev_ptr(opened.table, "table"), _dev_ptr(prev.totals, "prev") if prev else None,
+                                  _dev_ptr(arena_t, "arena") if arena_cap else None, arena_cap,
+                                  _dev_ptr(ops_t, "ops") if op_cap else None, op_cap, block_cap,
+                                  _dev_ptr(order_t, "order") if order else None,
+                                  _dev_ptr(mt_totals, "mt_totals") if order else None, _dev_ptr(totals, "totals"),
+                                  flags, _dev_ptr(workspace, "workspace"), workspace.numel(), _stream_ptr(stream))
+    if rc != 0:
+        raise LvError(f"lv_sst_scan_device: {lib().lv_last_error().decode()}")
+    return Scanned(arena_t, arena_cap, ops_t, op_cap, block_cap, totals, order_t if order else None,
+                   mt_totals if order else None, (opened, prev, workspace))

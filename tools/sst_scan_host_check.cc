@@ -1,0 +1,342 @@
+// Stand-alone check of the SSTable scan's host twin (csrc/sst_scan.cc, whose
+// core csrc/lvk/sst_scan.h is the text the kernels compile too) for sanitizer
+// builds on the CPU:
+//
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude
+//       tools/sst_scan_host_check.cc leveldb-rs_amd/csrc/sst_scan.cc leveldb-rs_amd/csrc/sst_get.cc
+//       leveldb-rs_amd/csrc/sst_build.cc leveldb-rs_amd/csrc/sst_format.cc leveldb-rs_amd/csrc/memtable.cc
+//       leveldb-rs_amd/csrc/crc32c_scalar.cc -o sst_scan_host_check && ./sst_scan_host_check [cases.bin]
+//
+// Every image, arena and op array is a heap block of exactly its size, so a
+// read or write one byte outside is a heap-buffer-overflow.  Three parts:
+//   1. tables built by lv_sst_build_host (the corner shapes of the format and
+//      pseudo-random ones over small blocks) are scanned: the result is
+//      compared entry by entry with the source in memtable order, then
+//      rebuilt with the same options and compared with the first image; a scan
+//      one op or one arena byte short reports the true counts and writes
+//      nothing;
+//   2. several thousand random flips and truncations of those images are
+//      scanned with the damaged image's own table and with the sound image's
+//      (a table the open did not write for this file), in buffers sized by the
+//      scan's own first pass: whatever the bytes say, reads stay inside the
+//      file and writes inside the counts reported;
+//   3. with a file argument, the cases python tests/sst_scan_cases.py dump FILE
+//      wrote (the damaged images, the block rules, foreign tables and flips the
+//      GPU suite replays, with the Python model's expected outputs).
+// Exits 0 when everything agrees.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "lvgpu/crc32c.h"
+#include "lvgpu/table.h"
+
+namespace lvgpu_internal {
+int set_error(int code, const char *) { return code; }
+}  // namespace lvgpu_internal
+
+namespace {
+
+int g_fail = 0;
+long g_scans = 0, g_ok = 0, g_corrupt = 0;
+#define CHECK(cond)                                                          \
+    do {                                                                     \
+        if (!(cond)) {                                                       \
+            if (g_fail < 50) std::fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
+            ++g_fail;                                                        \
+        }                                                                    \
+    } while (0)
+
+struct Item {
+    std::string key, value;
+    uint64_t tag;
+};
+
+uint64_t tag(uint64_t seq, uint32_t type) { return (seq << 8) | type; }
+
+// a heap copy of exactly n bytes (NULL for none)
+uint8_t *exact(const void *p, size_t n) {
+    if (!n) return nullptr;
+    uint8_t *q = static_cast<uint8_t *>(std::malloc(n));
+    std::memcpy(q, p, n);
+    return q;
+}
+
+uint64_t g_rng = 0x9e3779b97f4a7c15ull;
+uint64_t rnd() {
+    g_rng ^= g_rng << 13;
+    g_rng ^= g_rng >> 7;
+    g_rng ^= g_rng << 17;
+    return g_rng;
+}
+
+struct Scan {
+    lv_sst_scan_totals t{};
+    lv_mt_totals mt{};
+    uint8_t *arena = nullptr;
+    lv_wb_op *ops = nullptr;
+    uint32_t *order = nullptr;
+    void release() {
+        std::free(arena);
+        std::free(ops);
+        std::free(order);
+    }
+};
+
+// A sizing pass, then the scan into blocks of exactly the reported sizes.
+Scan scan(const uint8_t *file, const lv_sst_table &table) {
+    Scan s;
+    lv_sst_scan_totals size;
+    std::memset(&size, 0xEE, sizeof size);
+    CHECK(lv_sst_scan_host(file, &table, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, &size) == 0);
+    CHECK(size.reserved == 0 && (size.status & ~63ull) == 0);
+    ++g_scans;
+    const bool counted = !(size.status & ~(LV_SST_SCAN_OP_OVER | LV_SST_SCAN_ARENA_OVER));
+    if (!counted) CHECK(size.table_entries == 0 && size.table_bytes == 0 && size.runs == 0 && size.entries == 0);
+    const uint64_t ne = size.table_entries, nb = size.table_bytes;
+    s.arena = static_cast<uint8_t *>(nb ? std::malloc(nb) : nullptr);
+    s.ops = static_cast<lv_wb_op *>(ne ? std::malloc(ne * sizeof(lv_wb_op)) : nullptr);
+    s.order = static_cast<uint32_t *>(std::malloc(ne ? ne * 4 : 4));
+    std::memset(&s.t, 0xEE, sizeof s.t);
+    CHECK(lv_sst_scan_host(file, &table, nullptr, s.arena, nb, s.ops, ne, s.order, &s.mt, &s.t) == 0);
+    CHECK(s.t.table_entries == ne && s.t.table_bytes == nb && s.t.runs == size.runs);
+    CHECK(s.t.status == (counted ? 0 : size.status));
+    if (s.t.status) {
+        CHECK(s.mt.entries == 0 && s.mt.user_keys == 0 && s.mt.status == LV_MT_BUILD_UPSTREAM);
+        g_corrupt += s.t.status == LV_SST_SCAN_CORRUPT;
+    } else {
+        ++g_ok;
+        CHECK(s.mt.entries == ne && (s.mt.status == 0 || (s.mt.status == LV_SST_SCAN_MT_UNORDERED && !s.mt.user_keys)));
+        uint64_t at = 0;
+        for (uint64_t i = 0; i < ne; ++i) {  // packed, in order, inside the arena
+            CHECK(s.ops[i].key_off == at && s.ops[i].val_off == at + s.ops[i].key_len && s.order[i] == i);
+            at += static_cast<uint64_t>(s.ops[i].key_len) + s.ops[i].val_len;
+        }
+        CHECK(at == nb);
+    }
+    if (counted && ne) {  // one op short, one byte short: the true counts, nothing written
+        uint8_t *a = static_cast<uint8_t *>(nb > 1 ? std::malloc(nb - 1) : nullptr);
+        lv_wb_op *o = static_cast<lv_wb_op *>(ne > 1 ? std::malloc((ne - 1) * sizeof(lv_wb_op)) : nullptr);
+        if (a) std::memset(a, 0xA5, nb - 1);
+        if (o) std::memset(o, 0xA5, (ne - 1) * sizeof(lv_wb_op));
+        lv_sst_scan_totals t;
+        CHECK(lv_sst_scan_host(file, &table, nullptr, a, nb ? nb - 1 : 0, o, ne - 1, nullptr, nullptr, &t) == 0);
+        CHECK(t.status == (LV_SST_SCAN_OP_OVER | (nb ? LV_SST_SCAN_ARENA_OVER : 0)) && t.entries == ne && t.arena_bytes == nb);
+        for (uint64_t i = 0; a && i < nb - 1; ++i) CHECK(a[i] == 0xA5);
+        for (uint64_t i = 0; o && i < (ne - 1) * sizeof(lv_wb_op); ++i) CHECK(reinterpret_cast<uint8_t *>(o)[i] == 0xA5);
+        std::free(a);
+        std::free(o);
+    }
+    return s;
+}
+
+void fuzz(const uint8_t *image, uint64_t fb, const lv_sst_table &sound, int rounds) {
+    for (int round = 0; round < rounds; ++round) {
+        uint8_t *bad = exact(image, fb);
+        const int flips = round % 2 ? 1 + static_cast<int>(rnd() % 4) : 1;
+        // mostly inside the data blocks: damage to the footer or the index is the open's to find
+        const uint64_t span = round % 4 == 3 ? fb : sound.metaindex_offset ? sound.metaindex_offset : fb;
+        for (int f = 0; f < flips; ++f) bad[rnd() % span] = static_cast<uint8_t>(rnd());
+        const uint64_t cut = round % 16 == 15 ? rnd() % (fb + 1) : fb;  // now and then a truncated file
+        uint8_t *file = cut == fb ? bad : exact(bad, cut);
+        lv_sst_table t;
+        CHECK(lv_sst_open_host(file, cut, nullptr, 0, &t) == 0);
+        scan(file, t).release();
+        lv_sst_table foreign = sound;
+        foreign.file_bytes = cut;
+        scan(file, foreign).release();
+        if (file != bad) std::free(file);
+        std::free(bad);
+    }
+}
+
+void check_table(const std::vector<Item> &items, uint32_t bs, uint32_t ri, int fuzz_rounds) {
+    std::string p;
+    std::vector<lv_wb_op> ops;
+    for (const Item &it : items) {
+        lv_wb_op o{};
+        o.tag = it.tag;
+        o.key_off = p.size();
+        o.key_len = static_cast<uint32_t>(it.key.size());
+        p += it.key;
+        o.val_off = p.size();
+        o.val_len = static_cast<uint32_t>(it.value.size());
+        p += it.value;
+        ops.push_back(o);
+    }
+    const size_t n = items.size();
+    uint8_t *payload = exact(p.data(), p.size());
+    std::vector<uint32_t> order(n ? n : 1);
+    lv_mt_totals mt{};
+    CHECK(lv_memtable_build_host(payload, p.size(), n ? ops.data() : nullptr, n, n ? order.data() : nullptr, &mt) == 0);
+    const lv_sst_build_options opt{bs, ri};
+    lv_sst_build_totals size{}, tot{};
+    CHECK(lv_sst_build_host(payload, p.size(), ops.data(), order.data(), &mt, &opt, nullptr, 0, nullptr, 0, &size) == 0);
+    uint8_t *file = static_cast<uint8_t *>(size.file_bytes ? std::malloc(size.file_bytes) : nullptr);
+    uint64_t *handles = static_cast<uint64_t *>(std::malloc(16 * (size.data_blocks + 2)));
+    CHECK(lv_sst_build_host(payload, p.size(), ops.data(), order.data(), &mt, &opt, file, size.file_bytes, handles,
+                            size.data_blocks, &tot) == 0);
+    CHECK(tot.status == 0);
+    const uint64_t fb = tot.file_bytes;
+    lv_sst_table t;
+    CHECK(lv_sst_open_host(file, fb, nullptr, 0, &t) == 0 && t.status == 0);
+    // the scan: the source's entries in memtable order
+    Scan s = scan(file, t);
+    CHECK(s.t.status == 0 && s.t.table_entries == n && s.t.data_blocks == tot.data_blocks && s.t.entries == n);
+    CHECK(s.t.table_bytes == p.size() && s.t.arena_bytes == p.size());
+    CHECK(s.mt.status == 0 && s.mt.entries == n && s.mt.user_keys == mt.user_keys);
+    for (size_t i = 0; i < n && s.t.status == 0 && s.t.table_entries == n; ++i) {
+        const lv_wb_op &a = ops[order[i]], &b = s.ops[i];
+        CHECK(a.tag == b.tag && a.key_len == b.key_len && a.val_len == b.val_len);
+        CHECK(!a.key_len || std::memcmp(payload + a.key_off, s.arena + b.key_off, a.key_len) == 0);
+        CHECK(!a.val_len || std::memcmp(payload + a.val_off, s.arena + b.val_off, a.val_len) == 0);
+    }
+    // rebuilt with the same options: the first image
+    if (s.t.status == 0) {
+        lv_sst_build_totals again{};
+        uint8_t *file2 = static_cast<uint8_t *>(fb ? std::malloc(fb) : nullptr);
+        CHECK(lv_sst_build_host(s.arena, s.t.arena_bytes, s.ops, s.order, &s.mt, &opt, file2, fb, handles, tot.data_blocks,
+                                &again) == 0);
+        CHECK(again.status == 0 && again.file_bytes == fb && (!fb || std::memcmp(file, file2, fb) == 0));
+        std::free(file2);
+    }
+    // appended to itself: cumulative counts, the first copy untouched
+    if (n && s.t.status == 0) {
+        const uint64_t nb = s.t.table_bytes;
+        uint8_t *arena = static_cast<uint8_t *>(std::malloc(nb ? 2 * nb : 1));
+        lv_wb_op *both = static_cast<lv_wb_op *>(std::malloc(2 * n * sizeof(lv_wb_op)));
+        if (nb) std::memcpy(arena, s.arena, nb);
+        std::memcpy(both, s.ops, n * sizeof(lv_wb_op));
+        lv_sst_scan_totals t2;
+        CHECK(lv_sst_scan_host(file, &t, &s.t, arena, 2 * nb, both, 2 * n, nullptr, nullptr, &t2) == 0);
+        CHECK(t2.status == 0 && t2.entries == 2 * n && t2.arena_bytes == 2 * nb && t2.table_entries == n);
+        CHECK(!nb || (std::memcmp(arena, s.arena, nb) == 0 && std::memcmp(arena + nb, s.arena, nb) == 0));
+        for (size_t i = 0; i < n; ++i)
+            CHECK(both[n + i].key_off == both[i].key_off + nb && both[n + i].tag == both[i].tag && both[i].tag == s.ops[i].tag);
+        std::free(arena);
+        std::free(both);
+    }
+    s.release();
+    if (fb) fuzz(file, fb, t, fuzz_rounds);
+    std::free(handles);
+    std::free(file);
+    std::free(payload);
+}
+
+std::vector<Item> seq_items(size_t n) {
+    std::vector<Item> v;
+    for (size_t i = 0; i < n; ++i) {
+        char k[24];
+        std::snprintf(k, sizeof k, "%06zu", i);
+        v.push_back({k, "vvv", tag(100 + i, 1)});
+    }
+    return v;
+}
+
+uint64_t rd(const uint8_t *&p) {
+    uint64_t v;
+    std::memcpy(&v, p, 8);
+    p += 8;
+    return v;
+}
+
+// The dumped cases of tests/sst_scan_cases.py against the model's outputs.
+int replay(const char *path) {
+    FILE *f = std::fopen(path, "rb");
+    if (!f) {
+        std::fprintf(stderr, "cannot open %s\n", path);
+        return 1;
+    }
+    std::vector<uint8_t> buf;
+    uint8_t tmp[65536];
+    for (size_t n; (n = std::fread(tmp, 1, sizeof tmp, f)) > 0;) buf.insert(buf.end(), tmp, tmp + n);
+    std::fclose(f);
+    const uint8_t *p = buf.data();
+    const uint64_t cases = rd(p);
+    for (uint64_t c = 0; c < cases; ++c) {
+        const uint64_t len = rd(p);
+        const uint8_t *image = p;
+        p += len;
+        lv_sst_table t;
+        std::memcpy(&t, p, sizeof t);
+        p += sizeof t;
+        lv_sst_scan_totals want;
+        std::memcpy(&want, p, sizeof want);
+        p += sizeof want;
+        lv_mt_totals want_mt;
+        std::memcpy(&want_mt, p, sizeof want_mt);
+        p += sizeof want_mt;
+        const uint64_t nops = rd(p);
+        const uint8_t *wops = p;
+        p += nops * sizeof(lv_wb_op);
+        const uint64_t nb = rd(p);
+        const uint8_t *warena = p;
+        p += nb;
+        uint8_t *file = exact(image, t.file_bytes < len ? t.file_bytes : len);  // exactly what the table claims
+        Scan s = scan(file, t);
+        CHECK(std::memcmp(&s.t, &want, sizeof want) == 0);
+        CHECK(std::memcmp(&s.mt, &want_mt, sizeof want_mt) == 0);
+        if (s.t.status == 0 && s.t.table_entries == nops && s.t.table_bytes == nb) {
+            CHECK(!nops || std::memcmp(s.ops, wops, nops * sizeof(lv_wb_op)) == 0);
+            CHECK(!nb || std::memcmp(s.arena, warena, nb) == 0);
+        }
+        s.release();
+        std::free(file);
+    }
+    std::printf("replayed %llu dumped cases\n", static_cast<unsigned long long>(cases));
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    for (size_t n : {0, 1, 15, 16, 17, 32, 33}) check_table(seq_items(n), 4096, 16, 20);
+    check_table(seq_items(40), 64, 4, 600);
+    check_table(seq_items(40), 1, 1, 300);
+    check_table({{"a", "s", tag(1, 1)}, {"big", std::string(9000, 'B'), tag(2, 1)}, {"c", "t", tag(3, 1)}}, 4096, 16, 50);
+    std::vector<Item> high;
+    for (uint64_t s : {1ull, 2ull, 3ull, 200ull}) high.push_back({"same", "v", tag((s << 40) | 7, 1)});
+    for (uint32_t ri : {16u, 1u}) check_table(high, 4096, ri, 100);
+    const std::vector<Item> into = {{"a", "1", tag(5, 1)}, {std::string("a\x01\x05\0\0\0\0\0zz", 10), "2", tag(9, 1)},
+                                    {std::string("a\x01\x05", 3), "3", tag(1, 1)}};
+    for (uint32_t ri : {16u, 1u}) check_table(into, 4096, ri, 100);
+    check_table({{"dup", "same", tag(42, 1)}, {"dup", "same", tag(42, 1)}, {"dup", "same", tag(42, 1)},
+                 {"dup", "", tag(42, 0)}, {"dup", "", tag(42, 0)}}, 4096, 16, 50);
+    check_table({{"", "", tag(3, 1)}, {"", "", tag(2, 0)}, {"k", "", tag(1, 1)}, {"k", "", tag(9, 0)}, {"z", "val", tag(4, 1)}},
+                4096, 16, 50);
+    for (size_t w : {127, 128, 16383, 16384}) {
+        const std::string base(w, 'P');
+        check_table({{base + "a", "v", tag(1, 1)}, {base + "b", "w", tag(2, 1)}}, 1u << 20, 16, 10);
+        check_table({{"k", std::string(w, 'V'), tag(1, 1)}, {"l", std::string(w, 'W'), tag(2, 1)}}, 1u << 20, 16, 10);
+    }
+    {  // versions of one 5,000-byte key, and a shared stem with 1-byte differences
+        std::string stem(4999, '\0');
+        for (size_t i = 0; i < stem.size(); ++i) stem[i] = static_cast<char>(i);
+        std::vector<Item> items;
+        for (int c = 1; c < 40; ++c) items.push_back({stem + static_cast<char>(c), "v", tag(10 + c, 1)});
+        for (int c = 1; c < 40; ++c) items.push_back({stem, "stem", tag(c, c % 3 ? 1 : 0)});
+        check_table(items, 4096, 16, 20);
+        check_table(items, 1u << 20, 1024, 20);
+    }
+    // pseudo-random tables over small alphabets and small blocks
+    for (int trial = 0; trial < 200; ++trial) {
+        const unsigned sym = trial % 3 == 0 ? 2 : trial % 3 == 1 ? 4 : 256;
+        const size_t n = rnd() % 150;
+        std::vector<Item> items;
+        for (size_t i = 0; i < n; ++i) {
+            std::string k(rnd() % 14, '\0');
+            for (char &ch : k) ch = static_cast<char>('a' + rnd() % sym);
+            const uint32_t type = rnd() % 4 ? 1 : 0;
+            items.push_back({k, type ? std::string(rnd() % 6, 'v') : std::string(), tag(rnd() % 6, type)});
+        }
+        static const uint32_t sizes[] = {1, 32, 64, 300, 4096}, intervals[] = {1, 2, 4, 16};
+        check_table(items, sizes[rnd() % 5], intervals[rnd() % 4], 16);
+    }
+    int rc = 0;
+    if (argc > 1) rc = replay(argv[1]);
+    std::printf("%ld scans: %ld with status 0, %ld CORRUPT; %d failures\n", g_scans, g_ok, g_corrupt, g_fail);
+    return g_fail || rc ? 1 : 0;
+}
