@@ -128,6 +128,31 @@ int check_launch();
 
 constexpr size_t al16(size_t x) { return (x + 15) & ~static_cast<size_t>(15); }
 
+// ---- argument checks and workspaces of the device entry points ----
+// [a, a + ab) and [b, b + bb) share a byte (an empty range overlaps nothing).
+inline bool overlaps(const void *a, uint64_t ab, const void *b, uint64_t bb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return ab && bb && x < y + bb && y < x + ab;
+}
+// p is not a multiple of n (null is aligned).
+inline bool misaligned(const void *p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n != 0; }
+
+// A caller's workspace cut into 16-B aligned regions, in the order they are
+// taken.  A stage describes its workspace once, as the function that takes
+// its regions: with a null base it only measures (every region comes back
+// null and `at` ends as the bytes needed), with the caller's buffer it hands
+// out the pointers (to be used only once `at` is known to fit the buffer).
+struct Carve {
+    uint8_t *base;
+    size_t at = 0;
+    template <class T>
+    T *take(size_t count) {
+        const size_t o = at;
+        at += al16(count * sizeof(T));
+        return base ? reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(base) + o) : nullptr;
+    }
+};
+
 // ---- sort workspace (sort.hip) ----
 // Sorting workgroups and elements per workgroup for n buffers.
 uint64_t sort_wgs(uint64_t n, uint64_t *chunk);

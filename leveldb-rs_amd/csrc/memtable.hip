@@ -40,6 +40,7 @@
 #include "lv_internal.h"
 #include "lvh.h"
 #include "lvk/knobs.h"
+#include "lvk/stage.h"
 
 namespace lvk {
 
@@ -58,8 +59,6 @@ struct alignas(16) MtEnt {
 };
 static_assert(sizeof(MtEnt) == (kMtWords == 1 ? 16 : 32), "entry size");
 static_assert(sizeof(MtEnt) * kMtTile <= 65536, "a tile fits the LDS a workgroup may declare");
-
-typedef uint32_t mt_u4 __attribute__((ext_vector_type(4)));
 
 struct MtHead {  // workspace, zeroed by mt_init
     uint32_t bad, pad;
@@ -92,22 +91,6 @@ __device__ __forceinline__ uint64_t mt_entries(const MtArgs &A, uint32_t *status
         return 0;
     }
     return n;
-}
-
-__device__ __forceinline__ bool mt_extent_ok(uint64_t off, uint64_t len, uint64_t bytes) {
-    return off <= bytes && len <= bytes - off;  // u64, no wrap
-}
-
-__device__ __forceinline__ lv_wb_op mt_load_op(const lv_wb_op *p) {
-    const mt_u4 *q = reinterpret_cast<const mt_u4 *>(p);  // d_ops is 16-B aligned, an op is 32 bytes
-    const mt_u4 a = q[0], b = q[1];
-    lv_wb_op o;
-    o.tag = (static_cast<uint64_t>(a.y) << 32) | a.x;
-    o.key_off = (static_cast<uint64_t>(a.w) << 32) | a.z;
-    o.val_off = (static_cast<uint64_t>(b.y) << 32) | b.x;
-    o.key_len = b.z;
-    o.val_len = b.w;
-    return o;
 }
 
 // 8 bytes at any alignment as a big-endian word: all of them are key bytes.
@@ -183,9 +166,9 @@ __global__ __launch_bounds__(kMtThreads) void mt_tile_sort(const MtArgs A) {
         e.klen = kMtNone;
         e.idx = kMtNone;
         if (j < cnt) {
-            const lv_wb_op o = mt_load_op(A.ops + base + j);
-            if (!mt_extent_ok(o.key_off, o.key_len, A.payload_bytes) ||
-                !mt_extent_ok(o.val_off, o.val_len, A.payload_bytes)) {
+            const lv_wb_op o = load_op(A.ops + base + j);
+            if (!extent_ok(o.key_off, o.key_len, A.payload_bytes) ||
+                !extent_ok(o.val_off, o.val_len, A.payload_bytes)) {
                 bad = 1;
             } else {
                 const uint8_t *k = A.payload + o.key_off;
@@ -271,7 +254,7 @@ __global__ __launch_bounds__(kMtThreads) void mt_merge(const MtArgs A, uint32_t 
     const uint32_t q1 = q0 + kMtPer < total ? q0 + kMtPer : total;
     uint32_t x = static_cast<uint32_t>(mt_path(A, s, na, s + na, nb, q0)), y = q0 - x;
     constexpr uint32_t kQ = sizeof(MtEnt) / 16;  // an entry as 16-B register quads
-    mt_u4 r[kMtPer][kQ];
+    u32x4 r[kMtPer][kQ];
 #pragma unroll
     for (uint32_t k = 0; k < kMtPer; ++k) {
         uint32_t from = 0;
@@ -282,14 +265,14 @@ __global__ __launch_bounds__(kMtThreads) void mt_merge(const MtArgs A, uint32_t 
             y += !take_a;
         }
 #pragma unroll
-        for (uint32_t v = 0; v < kQ; ++v) r[k][v] = reinterpret_cast<const mt_u4 *>(s + from)[v];
+        for (uint32_t v = 0; v < kQ; ++v) r[k][v] = reinterpret_cast<const u32x4 *>(s + from)[v];
     }
     __syncthreads();
 #pragma unroll
     for (uint32_t k = 0; k < kMtPer; ++k)
         if (q0 + k < q1) {
 #pragma unroll
-            for (uint32_t v = 0; v < kQ; ++v) reinterpret_cast<mt_u4 *>(s + q0 + k)[v] = r[k][v];
+            for (uint32_t v = 0; v < kQ; ++v) reinterpret_cast<u32x4 *>(s + q0 + k)[v] = r[k][v];
         }
     __syncthreads();
     for (uint32_t j = tid; j < total; j += kMtThreads) out[o0 + j] = s[j];
@@ -364,7 +347,7 @@ __global__ __launch_bounds__(kMtThreads) void mt_get(const MtGetArgs G) {
         r.status = LV_MT_GET_NO_TABLE;
     } else if (seq > LV_MT_MAX_SEQUENCE) {
         r.status = LV_MT_GET_BAD_SEQ;
-    } else if (!mt_extent_ok(qo, ql, G.qkeys_bytes)) {
+    } else if (!extent_ok(qo, ql, G.qkeys_bytes)) {
         r.status = LV_MT_GET_BAD_QUERY;
     } else {
         const uint8_t *qk = G.qkeys + qo;
@@ -373,8 +356,8 @@ __global__ __launch_bounds__(kMtThreads) void mt_get(const MtGetArgs G) {
         bool ok = true;
         for (uint32_t it = 0; it < 64 && lo < hi; ++it) {
             const uint64_t mid = lo + (hi - lo) / 2;
-            const lv_wb_op o = mt_load_op(G.ops + G.order[mid]);
-            if (!mt_extent_ok(o.key_off, o.key_len, G.payload_bytes)) {  // not the build's arguments
+            const lv_wb_op o = load_op(G.ops + G.order[mid]);
+            if (!extent_ok(o.key_off, o.key_len, G.payload_bytes)) {  // not the build's arguments
                 ok = false;
                 break;
             }
@@ -388,8 +371,8 @@ __global__ __launch_bounds__(kMtThreads) void mt_get(const MtGetArgs G) {
             r.status = LV_MT_GET_NO_TABLE;
         } else if (lo < entries) {
             const uint32_t idx = G.order[lo];
-            const lv_wb_op o = mt_load_op(G.ops + idx);
-            if (mt_extent_ok(o.key_off, o.key_len, G.payload_bytes) &&
+            const lv_wb_op o = load_op(G.ops + idx);
+            if (extent_ok(o.key_off, o.key_len, G.payload_bytes) &&
                 mt_cmp_bytes(G.payload + o.key_off, o.key_len, qk, ql) == 0) {
                 r.op = idx;
                 if ((o.tag & 0xffu) == LV_WB_TYPE_VALUE) {
@@ -413,26 +396,11 @@ namespace {
 
 constexpr uint64_t kMaxOpCap = 0xfffffffeull;
 
-struct MtWs {
-    size_t head, buf0, buf1, total;
-    uint64_t tiles;
-    uint32_t passes;
-};
-MtWs mt_ws_layout(uint64_t cap) {
-    MtWs w;
-    w.tiles = (cap + lvk::kMtTile - 1) / lvk::kMtTile;
-    w.passes = 0;  // the run widths below cap
-    for (uint64_t run = lvk::kMtTile; run < cap; run <<= 1) ++w.passes;
-    w.head = 0;
-    w.buf0 = al16(sizeof(lvk::MtHead));
-    w.buf1 = w.buf0 + al16(cap * sizeof(lvk::MtEnt));
-    w.total = w.buf1 + al16(cap * sizeof(lvk::MtEnt));
-    return w;
-}
-
-bool overlaps(const void *a, uint64_t ab, const void *b, uint64_t bb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return ab && bb && x < y + bb && y < x + ab;
+// The workspace for op_cap = cap, region by region: fills A's workspace pointers.
+void mt_carve(Carve &C, uint64_t cap, lvk::MtArgs &A) {
+    A.head = C.take<lvk::MtHead>(1);
+    A.buf[0] = C.take<lvk::MtEnt>(cap);
+    A.buf[1] = C.take<lvk::MtEnt>(cap);
 }
 
 }  // namespace
@@ -440,7 +408,11 @@ bool overlaps(const void *a, uint64_t ab, const void *b, uint64_t bb) {
 extern "C" {
 
 size_t lv_memtable_build_workspace_bytes(size_t op_cap) {
-    return op_cap > kMaxOpCap ? 0 : mt_ws_layout(op_cap).total;
+    if (op_cap > kMaxOpCap) return 0;
+    lvk::MtArgs A{};
+    Carve C{nullptr};
+    mt_carve(C, op_cap, A);
+    return C.at;
 }
 
 int lv_memtable_build_device(const uint8_t *d_payload, size_t payload_bytes, const lv_wb_op *d_ops,
@@ -450,21 +422,22 @@ int lv_memtable_build_device(const uint8_t *d_payload, size_t payload_bytes, con
     g_err.clear();
     if (flags) return set_err(LV_ERR_INVALID, "unknown flag bits (none are defined)");
     if (!d_totals) return set_err(LV_ERR_INVALID, "null d_totals");
-    if (reinterpret_cast<uintptr_t>(d_totals) % 8) return set_err(LV_ERR_INVALID, "d_totals must be 8-byte aligned");
+    if (misaligned(d_totals, 8)) return set_err(LV_ERR_INVALID, "d_totals must be 8-byte aligned");
     if (!d_n_ops) return set_err(LV_ERR_INVALID, "null d_n_ops");
-    if (reinterpret_cast<uintptr_t>(d_n_ops) % 8) return set_err(LV_ERR_INVALID, "d_n_ops must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_upstream_status) % 8)
-        return set_err(LV_ERR_INVALID, "d_upstream_status must be 8-byte aligned");
+    if (misaligned(d_n_ops, 8)) return set_err(LV_ERR_INVALID, "d_n_ops must be 8-byte aligned");
+    if (misaligned(d_upstream_status, 8)) return set_err(LV_ERR_INVALID, "d_upstream_status must be 8-byte aligned");
     if (!d_payload && payload_bytes) return set_err(LV_ERR_INVALID, "null d_payload");
     if (op_cap > kMaxOpCap) return set_err(LV_ERR_INVALID, "op_cap too large for one build (at most 2^32 - 2)");
     if (op_cap && !d_ops) return set_err(LV_ERR_INVALID, "null d_ops");
-    if (reinterpret_cast<uintptr_t>(d_ops) % 16) return set_err(LV_ERR_INVALID, "d_ops must be 16-byte aligned");
+    if (misaligned(d_ops, 16)) return set_err(LV_ERR_INVALID, "d_ops must be 16-byte aligned");
     if (op_cap && !d_order) return set_err(LV_ERR_INVALID, "null d_order");
-    if (reinterpret_cast<uintptr_t>(d_order) % 4) return set_err(LV_ERR_INVALID, "d_order must be 4-byte aligned");
+    if (misaligned(d_order, 4)) return set_err(LV_ERR_INVALID, "d_order must be 4-byte aligned");
     if (!d_workspace) return set_err(LV_ERR_INVALID, "null workspace");
-    if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
-    const MtWs ws = mt_ws_layout(op_cap);
-    if (workspace_bytes < ws.total) return set_err(LV_ERR_INVALID, "workspace too small");
+    if (misaligned(d_workspace, 16)) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
+    lvk::MtArgs A{};
+    Carve C{static_cast<uint8_t *>(d_workspace)};
+    mt_carve(C, op_cap, A);
+    if (workspace_bytes < C.at) return set_err(LV_ERR_INVALID, "workspace too small");
     const uint64_t order_bytes = static_cast<uint64_t>(op_cap) * sizeof(uint32_t);
     if (overlaps(d_order, order_bytes, d_ops, static_cast<uint64_t>(op_cap) * sizeof(lv_wb_op)))
         return set_err(LV_ERR_INVALID, "d_order overlaps d_ops");
@@ -473,9 +446,7 @@ int lv_memtable_build_device(const uint8_t *d_payload, size_t payload_bytes, con
     DevCtx *c = nullptr;
     if (int rc = current_ctx(&c)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *wb = static_cast<uint8_t *>(d_workspace);
 
-    lvk::MtArgs A{};
     A.payload = d_payload;
     A.payload_bytes = payload_bytes;
     A.ops = d_ops;
@@ -484,16 +455,15 @@ int lv_memtable_build_device(const uint8_t *d_payload, size_t payload_bytes, con
     A.op_cap = op_cap;
     A.order = d_order;
     A.totals = d_totals;
-    A.head = reinterpret_cast<lvk::MtHead *>(wb + ws.head);
-    A.buf[0] = reinterpret_cast<lvk::MtEnt *>(wb + ws.buf0);
-    A.buf[1] = reinterpret_cast<lvk::MtEnt *>(wb + ws.buf1);
 
     const dim3 b(lvk::kMtThreads);
-    const uint32_t tiles = static_cast<uint32_t>(ws.tiles);
+    const uint32_t tiles = static_cast<uint32_t>((static_cast<uint64_t>(op_cap) + lvk::kMtTile - 1) / lvk::kMtTile);
+    uint32_t passes = 0;  // the run widths below op_cap
+    for (uint64_t run = lvk::kMtTile; run < op_cap; run <<= 1) ++passes;
     hipLaunchKernelGGL(lvk::mt_init, dim3(1), dim3(1), 0, s, A);
     if (tiles) {
         hipLaunchKernelGGL(lvk::mt_tile_sort, dim3(tiles), b, 0, s, A);
-        for (uint32_t p = 0; p < ws.passes; ++p) hipLaunchKernelGGL(lvk::mt_merge, dim3(tiles), b, 0, s, A, p);
+        for (uint32_t p = 0; p < passes; ++p) hipLaunchKernelGGL(lvk::mt_merge, dim3(tiles), b, 0, s, A, p);
         const uint32_t og = static_cast<uint32_t>((static_cast<uint64_t>(op_cap) + lvk::kMtThreads - 1) / lvk::kMtThreads);
         hipLaunchKernelGGL(lvk::mt_order, dim3(og), b, 0, s, A);
     }
@@ -510,19 +480,19 @@ int lv_memtable_get_device(const uint8_t *d_payload, size_t payload_bytes, const
     g_err.clear();
     if (flags) return set_err(LV_ERR_INVALID, "unknown flag bits (none are defined)");
     if (!d_totals) return set_err(LV_ERR_INVALID, "null d_totals");
-    if (reinterpret_cast<uintptr_t>(d_totals) % 8) return set_err(LV_ERR_INVALID, "d_totals must be 8-byte aligned");
+    if (misaligned(d_totals, 8)) return set_err(LV_ERR_INVALID, "d_totals must be 8-byte aligned");
     if (!d_payload && payload_bytes) return set_err(LV_ERR_INVALID, "null d_payload");
     if (!d_qkeys && qkeys_bytes) return set_err(LV_ERR_INVALID, "null d_qkeys");
-    if (reinterpret_cast<uintptr_t>(d_ops) % 16) return set_err(LV_ERR_INVALID, "d_ops must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_order) % 4) return set_err(LV_ERR_INVALID, "d_order must be 4-byte aligned");
+    if (misaligned(d_ops, 16)) return set_err(LV_ERR_INVALID, "d_ops must be 16-byte aligned");
+    if (misaligned(d_order, 4)) return set_err(LV_ERR_INVALID, "d_order must be 4-byte aligned");
     if (!d_ops != !d_order) return set_err(LV_ERR_INVALID, "null d_ops or d_order (both or neither)");
     if (nq > kMaxOpCap) return set_err(LV_ERR_INVALID, "nq too large for one call (at most 2^32 - 2)");
     if (nq && (!d_q_off || !d_q_len || !d_q_seq)) return set_err(LV_ERR_INVALID, "null query array");
     if (nq && !d_results) return set_err(LV_ERR_INVALID, "null d_results");
-    if (reinterpret_cast<uintptr_t>(d_q_off) % 8 || reinterpret_cast<uintptr_t>(d_q_seq) % 8)
+    if (misaligned(d_q_off, 8) || misaligned(d_q_seq, 8))
         return set_err(LV_ERR_INVALID, "d_q_off and d_q_seq must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_q_len) % 4) return set_err(LV_ERR_INVALID, "d_q_len must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_results) % 8) return set_err(LV_ERR_INVALID, "d_results must be 8-byte aligned");
+    if (misaligned(d_q_len, 4)) return set_err(LV_ERR_INVALID, "d_q_len must be 4-byte aligned");
+    if (misaligned(d_results, 8)) return set_err(LV_ERR_INVALID, "d_results must be 8-byte aligned");
     DevCtx *c = nullptr;
     if (int rc = current_ctx(&c)) return rc;
     if (!nq) return LV_OK;

@@ -55,6 +55,10 @@
 // trailer launches), never on the device-side counts.  No workgroup
 // waits on another inside a launch; every search loop is bounded.  All sizes
 // and positions are u64.
+//
+// The tile scan, the carries' wave scan, the shared copy and the op loads are
+// lvk/stage.h's (tile_scan, carry_scan, group_copy, load_op), instantiated
+// with this file's tile, thread count and copy knobs.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -64,6 +68,7 @@
 #include "lv_internal.h"
 #include "lvh.h"
 #include "lvk/knobs.h"
+#include "lvk/stage.h"
 
 namespace lvk {
 
@@ -78,8 +83,6 @@ static_assert(kSbTile % kSbThreads == 0 && kSbTile >= kSbMaxR, "a tile holds eve
 static_assert(kSbTile * 16 <= 65536, "two u64 scan arrays fit the LDS a workgroup may declare");
 static_assert(kSbWaveCopy >= 16, "a wave copy has at least one granule");
 static_assert(kSbCopyLanes >= 16 && 64 % kSbCopyLanes == 0, "a copy's lanes cover a ragged head or tail of 15 bytes");
-
-typedef uint32_t sb_u4 __attribute__((ext_vector_type(4)));
 
 struct SbHead {  // workspace, zeroed by sb_init
     uint32_t bad, large, go, pad;
@@ -119,22 +122,6 @@ struct SbArgs {
 __device__ __forceinline__ uint64_t sb_entries(const SbArgs &A) {
     const uint64_t n = A.mt->entries;
     return (A.mt->status || n > A.op_cap) ? 0 : n;
-}
-
-__device__ __forceinline__ bool sb_extent_ok(uint64_t off, uint64_t len, uint64_t bytes) {
-    return off <= bytes && len <= bytes - off;  // u64, no wrap
-}
-
-__device__ __forceinline__ lv_wb_op sb_load_op(const lv_wb_op *p) {
-    const sb_u4 *q = reinterpret_cast<const sb_u4 *>(p);  // d_ops is 16-B aligned, an op is 32 bytes
-    const sb_u4 a = q[0], b = q[1];
-    lv_wb_op o;
-    o.tag = (static_cast<uint64_t>(a.y) << 32) | a.x;
-    o.key_off = (static_cast<uint64_t>(a.w) << 32) | a.z;
-    o.val_off = (static_cast<uint64_t>(b.y) << 32) | b.x;
-    o.key_len = b.z;
-    o.val_len = b.w;
-    return o;
 }
 
 __device__ __forceinline__ uint32_t sb_varint_len(uint64_t v) {
@@ -192,22 +179,6 @@ __device__ __forceinline__ uint64_t sb_shared(const SbArgs &A, const lv_wb_op &p
     return s;
 }
 
-// In-place inclusive scan of s[0, kSbTile) with stride st (s[j] += s[j - st] chains).
-__device__ __forceinline__ void sb_tile_scan(uint64_t *s, uint32_t st, uint32_t tid) {
-    for (uint32_t off = st; off < kSbTile; off <<= 1) {
-        uint64_t v[kSbPer];
-#pragma unroll
-        for (uint32_t k = 0; k < kSbPer; ++k) {
-            const uint32_t j = tid + k * kSbThreads;
-            v[k] = j >= off ? s[j - off] : 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t k = 0; k < kSbPer; ++k) s[tid + k * kSbThreads] += v[k];
-        __syncthreads();
-    }
-}
-
 // The global scans from the tile-local ones and the scanned carries.
 __device__ __forceinline__ uint64_t sb_P(const SbArgs &A, uint64_t i) { return A.Pl[i] + A.cP[i / kSbTile]; }
 __device__ __forceinline__ uint64_t sb_S(const SbArgs &A, uint64_t i) {
@@ -252,10 +223,10 @@ __global__ __launch_bounds__(kSbThreads) void sb_sizes(const SbArgs A) {
             if (oi >= A.op_cap || pi >= A.op_cap) {
                 bad = 1;
             } else {
-                const lv_wb_op o = sb_load_op(A.ops + oi), p = sb_load_op(A.ops + pi);
-                if (!sb_extent_ok(o.key_off, o.key_len, A.payload_bytes) ||
-                    !sb_extent_ok(o.val_off, o.val_len, A.payload_bytes) ||
-                    !sb_extent_ok(p.key_off, p.key_len, A.payload_bytes)) {
+                const lv_wb_op o = load_op(A.ops + oi), p = load_op(A.ops + pi);
+                if (!extent_ok(o.key_off, o.key_len, A.payload_bytes) ||
+                    !extent_ok(o.val_off, o.val_len, A.payload_bytes) ||
+                    !extent_ok(p.key_off, p.key_len, A.payload_bytes)) {
                     bad = 1;
                 } else {
                     if (i) sh = sb_shared(A, p, o);
@@ -273,8 +244,8 @@ __global__ __launch_bounds__(kSbThreads) void sb_sizes(const SbArgs A) {
         if (tid == 0) atomicOr(&A.head->bad, 1u);
         return;
     }
-    sb_tile_scan(s_p, 1, tid);
-    sb_tile_scan(s_s, A.R, tid);
+    tile_scan<kSbTile, kSbThreads>(s_p, 1, tid);
+    tile_scan<kSbTile, kSbThreads>(s_s, A.R, tid);
 #pragma unroll
     for (uint32_t k = 0; k < kSbPer; ++k) {
         const uint32_t j = tid + k * kSbThreads;
@@ -288,15 +259,6 @@ __global__ __launch_bounds__(kSbThreads) void sb_sizes(const SbArgs A) {
         const uint32_t r0 = static_cast<uint32_t>((c + A.R - base % A.R) % A.R);
         A.cS[static_cast<uint64_t>(blockIdx.x) * A.R + c] = r0 < cnt ? s_s[r0 + (cnt - 1 - r0) / A.R * A.R] : 0;
     }
-}
-
-__device__ __forceinline__ uint64_t sb_wave_incl(uint64_t v, uint32_t lane) {
-#pragma unroll
-    for (uint32_t o = 1; o < 64; o <<= 1) {
-        const uint64_t u = __shfl_up(static_cast<unsigned long long>(v), o, 64);
-        if (lane >= o) v += u;
-    }
-    return v;
 }
 
 // Kernel 2: the exclusive scan over the tiles of column c, in place; one wave
@@ -325,14 +287,7 @@ __global__ __launch_bounds__(kSbThreads) void sb_carry(const SbArgs A, uint32_t 
         col = A.cI;
         total = &A.head->idx_bytes;
     }
-    uint64_t run = 0;
-    for (uint64_t t0 = 0; t0 < tiles; t0 += 64) {  // wave-uniform
-        const uint64_t t = t0 + lane;
-        const uint64_t v = t < tiles ? col[t * stride] : 0;
-        const uint64_t inc = sb_wave_incl(v, lane);
-        if (t < tiles) col[t * stride] = run + inc - v;
-        run += __shfl(static_cast<unsigned long long>(inc), 63, 64);
-    }
+    const uint64_t run = carry_scan(col, stride, tiles, lane);
     if (total && lane == 0) *total = run;
 }
 
@@ -393,8 +348,8 @@ __global__ __launch_bounds__(kSbThreads) void sb_layout(const SbArgs A) {
     }
     if (large) atomicOr(&A.head->large, 1u);
     __syncthreads();
-    sb_tile_scan(s_c, 1, tid);
-    sb_tile_scan(s_b, 1, tid);
+    tile_scan<kSbTile, kSbThreads>(s_c, 1, tid);
+    tile_scan<kSbTile, kSbThreads>(s_b, 1, tid);
 #pragma unroll
     for (uint32_t k = 0; k < kSbPer; ++k) {
         const uint32_t j = tid + k * kSbThreads;
@@ -420,7 +375,7 @@ __device__ __forceinline__ SbSep sb_separator(const SbArgs &A, uint64_t e, uint6
     const uint8_t *ka = A.payload + o.key_off;
     const uint64_t la = o.key_len;
     if (e + 1 < n) {
-        const lv_wb_op b = sb_load_op(A.ops + A.order[e + 1]);
+        const lv_wb_op b = load_op(A.ops + A.order[e + 1]);
         const uint64_t lb = b.key_len, m = la < lb ? la : lb;
         uint64_t d = A.shared[e + 1];  // over internal keys: the user keys' is no longer than either
         if (d > m) d = m;
@@ -471,12 +426,12 @@ __global__ __launch_bounds__(kSbThreads) void sb_index(const SbArgs A) {
                 A.wsh[2 * b] = off;
                 A.wsh[2 * b + 1] = raw;
             }
-            v = sb_index_entry(A, e, n, sb_load_op(A.ops + A.order[e]), off, raw).size;
+            v = sb_index_entry(A, e, n, load_op(A.ops + A.order[e]), off, raw).size;
         }
         s_i[j] = v;
     }
     __syncthreads();
-    sb_tile_scan(s_i, 1, tid);
+    tile_scan<kSbTile, kSbThreads>(s_i, 1, tid);
 #pragma unroll
     for (uint32_t k = 0; k < kSbPer; ++k) {
         const uint32_t j = tid + k * kSbThreads;
@@ -521,47 +476,6 @@ __global__ void sb_plan(const SbArgs A) {
     *A.totals = t;
 }
 
-// len bytes from src to dst by kSbCopyLanes lanes: dst's ragged head and tail byte
-// by byte, between them 16-byte granules of dst's alignment (an unaligned
-// load, an aligned store).  len >= 16.
-__device__ __forceinline__ void sb_wave_copy(uint8_t *dst, const uint8_t *src, uint64_t len, uint32_t lane) {
-    const uint32_t head = static_cast<uint32_t>((16u - (reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u);
-    const uint64_t gran = (len - head) / 16;
-    const uint32_t tail = static_cast<uint32_t>((len - head) % 16);
-    if (lane < head) dst[lane] = src[lane];
-    for (uint64_t g = lane; g < gran; g += kSbCopyLanes) {
-        sb_u4 v;
-        __builtin_memcpy(&v, src + head + g * 16, 16);
-        *reinterpret_cast<sb_u4 *>(dst + head + g * 16) = v;
-    }
-    if (lane < tail) dst[head + gran * 16 + lane] = src[head + gran * 16 + lane];
-}
-
-// A lane's copy job: short ones it does itself, the others its wave does, a
-// group of kSbCopyLanes lanes per job and 64 / kSbCopyLanes jobs at a time.
-__device__ __forceinline__ void sb_copy(uint8_t *dst, const uint8_t *src, uint64_t len, uint32_t lane) {
-    constexpr uint32_t kGroups = 64 / kSbCopyLanes;
-    if (len < kSbWaveCopy)
-        for (uint64_t i = 0; i < len; ++i) dst[i] = src[i];
-    uint64_t todo = __ballot(len >= kSbWaveCopy);
-    const uint32_t grp = lane / kSbCopyLanes;
-    while (todo) {  // wave-uniform
-        int l = -1;  // this group's job: the grp-th lane of todo, if there is one
-        uint64_t t = todo;
-#pragma unroll
-        for (uint32_t k = 0; k < kGroups; ++k) {
-            if (k <= grp) l = t ? __ffsll(static_cast<unsigned long long>(t)) - 1 : -1;
-            t &= t - 1;  // (0 stays 0)
-        }
-        todo = t;
-        const int from = l < 0 ? 0 : l;
-        uint8_t *d = reinterpret_cast<uint8_t *>(__shfl(reinterpret_cast<unsigned long long>(dst), from, 64));
-        const uint8_t *sp = reinterpret_cast<const uint8_t *>(__shfl(reinterpret_cast<unsigned long long>(src), from, 64));
-        const uint64_t m = __shfl(static_cast<unsigned long long>(len), from, 64);
-        if (l >= 0) sb_wave_copy(d, sp, m, lane % kSbCopyLanes);
-    }
-}
-
 // Kernel 8: the entries, the restart arrays, the index entries.  Every lane of
 // a wave stays to the end: the long copies are the wave's.
 __global__ __launch_bounds__(kSbThreads) void sb_emit(const SbArgs A) {
@@ -576,7 +490,7 @@ __global__ __launch_bounds__(kSbThreads) void sb_emit(const SbArgs A) {
     const uint8_t *ks = nullptr, *vs = nullptr, *xs = nullptr;
     uint64_t kn = 0, vn = 0, xn = 0;
     if (on) {
-        const lv_wb_op o = sb_load_op(A.ops + A.order[i]);
+        const lv_wb_op o = load_op(A.ops + A.order[i]);
         const uint64_t b = A.Cl[i] + A.cC[i / kSbTile] - 1;  // < block_cap: the plan checked
         const uint64_t s = A.blk_start[b], boff = A.wsh[2 * b], raw = A.wsh[2 * b + 1];
         const bool restart = (i - s) % A.R == 0;
@@ -605,7 +519,7 @@ __global__ __launch_bounds__(kSbThreads) void sb_emit(const SbArgs A) {
             sb_put_fixed32(arr + 4 * nrest, static_cast<uint32_t>(nrest));
             // the block's index entry: shared = 0, the key, the handle
             const uint64_t e = s + cnt - 1;
-            const lv_wb_op le = sb_load_op(A.ops + A.order[e]);
+            const lv_wb_op le = load_op(A.ops + A.order[e]);
             const SbIndexEntry x = sb_index_entry(A, e, n, le, boff, raw);
             const uint64_t at = A.Il[i] + A.cI[i / kSbTile] - x.size;
             uint8_t *ix = A.file + A.head->index_off;
@@ -628,9 +542,9 @@ __global__ __launch_bounds__(kSbThreads) void sb_emit(const SbArgs A) {
             q = sb_put_varint(q, raw);
         }
     }
-    sb_copy(kd, ks, kn, lane);
-    sb_copy(vd, vs, vn, lane);
-    if (__ballot(xn != 0)) sb_copy(xd, xs, xn, lane);
+    group_copy<kSbCopyLanes, kSbWaveCopy>(kd, ks, kn, lane);
+    group_copy<kSbCopyLanes, kSbWaveCopy>(vd, vs, vn, lane);
+    if (__ballot(xn != 0)) group_copy<kSbCopyLanes, kSbWaveCopy>(xd, xs, xn, lane);
 }
 
 // Kernel 9: d_handles and the workspace copy's padding; one thread writes the
@@ -689,47 +603,37 @@ namespace {
 constexpr uint64_t kMaxOpCap = 0xfffffffeull;
 constexpr uint64_t kMaxBlockCap = 0xfffffffcull;
 
-struct SbWs {
-    size_t head, shared, Pl, Sl, cP, cS, nxt, J0, J1, F, Cl, Bl, Il, cC, cB, cI, blk_start, wsh, idx, crc_ws, crc_ws_bytes, total;
-    uint64_t tiles;
-};
-SbWs sb_ws_layout(uint64_t cap, uint64_t bc) {
-    SbWs w;
-    w.tiles = (cap + lvk::kSbTile - 1) / lvk::kSbTile;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += al16(bytes);
-        return o;
-    };
-    w.head = take(sizeof(lvk::SbHead));
-    w.shared = take(cap * 8);
-    w.Pl = take(cap * 8);
-    w.Sl = take(cap * 8);
-    w.cP = take(w.tiles * 8);
-    w.cS = take(w.tiles * lvk::kSbMaxR * 8);
-    w.nxt = take(cap * 4);
-    w.J0 = take(cap * 4);
-    w.J1 = take(cap * 4);
-    w.F = take(cap);
-    w.Cl = take(cap * 8);
-    w.Bl = take(cap * 8);
-    w.Il = take(cap * 8);
-    w.cC = take(w.tiles * 8);
-    w.cB = take(w.tiles * 8);
-    w.cI = take(w.tiles * 8);
-    w.blk_start = take(bc * 4);
-    w.wsh = take((bc + 2) * 16);
-    w.idx = take(16);
-    w.crc_ws_bytes = lv_crc32c_workspace_bytes(1);
-    w.crc_ws = take(w.crc_ws_bytes);
-    w.total = at;
-    return w;
-}
+constexpr uint64_t sb_tiles(uint64_t cap) { return (cap + lvk::kSbTile - 1) / lvk::kSbTile; }
 
-bool overlaps(const void *a, uint64_t ab, const void *b, uint64_t bb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return ab && bb && x < y + bb && y < x + ab;
+// The workspace for op_cap = cap and block_cap = bc, region by region: fills
+// A's workspace pointers and returns the CRC batch's sub-workspace
+// (lv_crc32c_workspace_bytes(1) bytes).
+uint8_t *sb_carve(Carve &C, uint64_t cap, uint64_t bc, lvk::SbArgs &A) {
+    const uint64_t tiles = sb_tiles(cap);
+    A.head = C.take<lvk::SbHead>(1);
+    A.shared = C.take<uint64_t>(cap);
+    A.Pl = C.take<uint64_t>(cap);
+    A.Sl = C.take<uint64_t>(cap);
+    A.cP = C.take<uint64_t>(tiles);
+    A.cS = C.take<uint64_t>(tiles * lvk::kSbMaxR);
+    A.nxt = C.take<uint32_t>(cap);
+    A.J[0] = C.take<uint32_t>(cap);
+    A.J[1] = C.take<uint32_t>(cap);
+    A.F = C.take<uint8_t>(cap);
+    A.Cl = C.take<uint64_t>(cap);
+    A.Bl = C.take<uint64_t>(cap);
+    A.Il = C.take<uint64_t>(cap);
+    A.cC = C.take<uint64_t>(tiles);
+    A.cB = C.take<uint64_t>(tiles);
+    A.cI = C.take<uint64_t>(tiles);
+    A.blk_start = C.take<uint32_t>(bc);
+    A.wsh = C.take<uint64_t>(2 * (bc + 2));
+    if (uint32_t *idx = C.take<uint32_t>(4)) {  // the one-buffer batch: {offset (u64), length, crc}
+        A.idx_off = reinterpret_cast<uint64_t *>(idx);
+        A.idx_len = idx + 2;
+        A.idx_crc = idx + 3;
+    }
+    return C.take<uint8_t>(lv_crc32c_workspace_bytes(1));
 }
 
 }  // namespace
@@ -737,7 +641,11 @@ bool overlaps(const void *a, uint64_t ab, const void *b, uint64_t bb) {
 extern "C" {
 
 size_t lv_sst_build_workspace_bytes(size_t op_cap, size_t block_cap) {
-    return (op_cap > kMaxOpCap || block_cap > kMaxBlockCap) ? 0 : sb_ws_layout(op_cap, block_cap).total;
+    if (op_cap > kMaxOpCap || block_cap > kMaxBlockCap) return 0;
+    lvk::SbArgs A{};
+    Carve C{nullptr};
+    sb_carve(C, op_cap, block_cap, A);
+    return C.at;
 }
 
 int lv_sst_build_device(const uint8_t *d_payload, size_t payload_bytes, const lv_wb_op *d_ops, const uint32_t *d_order,
@@ -753,25 +661,26 @@ int lv_sst_build_device(const uint8_t *d_payload, size_t payload_bytes, const lv
     if (ri < 1 || ri > LV_SST_MAX_RESTART_INTERVAL)
         return set_err(LV_ERR_INVALID, "restart_interval must be in [1, 1024]");
     if (!d_totals) return set_err(LV_ERR_INVALID, "null d_totals");
-    if (reinterpret_cast<uintptr_t>(d_totals) % 8) return set_err(LV_ERR_INVALID, "d_totals must be 8-byte aligned");
+    if (misaligned(d_totals, 8)) return set_err(LV_ERR_INVALID, "d_totals must be 8-byte aligned");
     if (!d_mt_totals) return set_err(LV_ERR_INVALID, "null d_mt_totals");
-    if (reinterpret_cast<uintptr_t>(d_mt_totals) % 8)
-        return set_err(LV_ERR_INVALID, "d_mt_totals must be 8-byte aligned");
+    if (misaligned(d_mt_totals, 8)) return set_err(LV_ERR_INVALID, "d_mt_totals must be 8-byte aligned");
     if (!d_payload && payload_bytes) return set_err(LV_ERR_INVALID, "null d_payload");
     if (op_cap > kMaxOpCap) return set_err(LV_ERR_INVALID, "op_cap too large for one build (at most 2^32 - 2)");
     if (block_cap > kMaxBlockCap) return set_err(LV_ERR_INVALID, "block_cap too large for one build (at most 2^32 - 4)");
     if (op_cap && !d_ops) return set_err(LV_ERR_INVALID, "null d_ops");
-    if (reinterpret_cast<uintptr_t>(d_ops) % 16) return set_err(LV_ERR_INVALID, "d_ops must be 16-byte aligned");
+    if (misaligned(d_ops, 16)) return set_err(LV_ERR_INVALID, "d_ops must be 16-byte aligned");
     if (op_cap && !d_order) return set_err(LV_ERR_INVALID, "null d_order");
-    if (reinterpret_cast<uintptr_t>(d_order) % 4) return set_err(LV_ERR_INVALID, "d_order must be 4-byte aligned");
+    if (misaligned(d_order, 4)) return set_err(LV_ERR_INVALID, "d_order must be 4-byte aligned");
     if (file_cap && !d_file) return set_err(LV_ERR_INVALID, "null d_file");
-    if (reinterpret_cast<uintptr_t>(d_file) % 16) return set_err(LV_ERR_INVALID, "d_file must be 16-byte aligned");
+    if (misaligned(d_file, 16)) return set_err(LV_ERR_INVALID, "d_file must be 16-byte aligned");
     if (!d_handles) return set_err(LV_ERR_INVALID, "null d_handles");
-    if (reinterpret_cast<uintptr_t>(d_handles) % 8) return set_err(LV_ERR_INVALID, "d_handles must be 8-byte aligned");
+    if (misaligned(d_handles, 8)) return set_err(LV_ERR_INVALID, "d_handles must be 8-byte aligned");
     if (!d_workspace) return set_err(LV_ERR_INVALID, "null workspace");
-    if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
-    const SbWs ws = sb_ws_layout(op_cap, block_cap);
-    if (workspace_bytes < ws.total) return set_err(LV_ERR_INVALID, "workspace too small");
+    if (misaligned(d_workspace, 16)) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
+    lvk::SbArgs A{};
+    Carve C{static_cast<uint8_t *>(d_workspace)};
+    uint8_t *crc_ws = sb_carve(C, op_cap, block_cap, A);
+    if (workspace_bytes < C.at) return set_err(LV_ERR_INVALID, "workspace too small");
     const uint64_t handle_bytes = (static_cast<uint64_t>(block_cap) + 2) * 16;
     const struct {
         const void *p;
@@ -789,9 +698,7 @@ int lv_sst_build_device(const uint8_t *d_payload, size_t payload_bytes, const lv
     DevCtx *c = nullptr;
     if (int rc = current_ctx(&c)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *wb = static_cast<uint8_t *>(d_workspace);
 
-    lvk::SbArgs A{};
     A.payload = d_payload;
     A.payload_bytes = payload_bytes;
     A.ops = d_ops;
@@ -805,30 +712,9 @@ int lv_sst_build_device(const uint8_t *d_payload, size_t payload_bytes, const lv
     A.handles = d_handles;
     A.block_cap = block_cap;
     A.totals = d_totals;
-    A.head = reinterpret_cast<lvk::SbHead *>(wb + ws.head);
-    A.shared = reinterpret_cast<uint64_t *>(wb + ws.shared);
-    A.Pl = reinterpret_cast<uint64_t *>(wb + ws.Pl);
-    A.Sl = reinterpret_cast<uint64_t *>(wb + ws.Sl);
-    A.cP = reinterpret_cast<uint64_t *>(wb + ws.cP);
-    A.cS = reinterpret_cast<uint64_t *>(wb + ws.cS);
-    A.nxt = reinterpret_cast<uint32_t *>(wb + ws.nxt);
-    A.J[0] = reinterpret_cast<uint32_t *>(wb + ws.J0);
-    A.J[1] = reinterpret_cast<uint32_t *>(wb + ws.J1);
-    A.F = wb + ws.F;
-    A.Cl = reinterpret_cast<uint64_t *>(wb + ws.Cl);
-    A.Bl = reinterpret_cast<uint64_t *>(wb + ws.Bl);
-    A.Il = reinterpret_cast<uint64_t *>(wb + ws.Il);
-    A.cC = reinterpret_cast<uint64_t *>(wb + ws.cC);
-    A.cB = reinterpret_cast<uint64_t *>(wb + ws.cB);
-    A.cI = reinterpret_cast<uint64_t *>(wb + ws.cI);
-    A.blk_start = reinterpret_cast<uint32_t *>(wb + ws.blk_start);
-    A.wsh = reinterpret_cast<uint64_t *>(wb + ws.wsh);
-    A.idx_off = reinterpret_cast<uint64_t *>(wb + ws.idx);
-    A.idx_len = reinterpret_cast<uint32_t *>(wb + ws.idx + 8);
-    A.idx_crc = reinterpret_cast<uint32_t *>(wb + ws.idx + 12);
 
     const dim3 b(lvk::kSbThreads);
-    const uint32_t tiles = static_cast<uint32_t>(ws.tiles);
+    const uint32_t tiles = static_cast<uint32_t>(sb_tiles(op_cap));
     const uint32_t eg = static_cast<uint32_t>((static_cast<uint64_t>(op_cap) + lvk::kSbThreads - 1) / lvk::kSbThreads);
     constexpr uint32_t kWaves = lvk::kSbThreads / 64;
     hipLaunchKernelGGL(lvk::sb_init, dim3(1), dim3(1), 0, s, A);
@@ -854,7 +740,7 @@ int lv_sst_build_device(const uint8_t *d_payload, size_t payload_bytes, const lv
             return rc;
         // ... and the index block as a one-buffer batch (an empty one when nothing was written)
         if (int rc = lv_crc32c_batch_device_ws(d_file, A.idx_off, A.idx_len, nullptr, A.idx_crc, 1, LV_CRC_MASK,
-                                               wb + ws.crc_ws, ws.crc_ws_bytes, stream))
+                                               crc_ws, lv_crc32c_workspace_bytes(1), stream))
             return rc;
         hipLaunchKernelGGL(lvk::sb_index_trailer, dim3(1), dim3(1), 0, s, A);
         if (int rc = check_launch()) return rc;

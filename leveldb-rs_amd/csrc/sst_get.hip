@@ -33,6 +33,7 @@
 #include "lv_internal.h"
 #include "lvh.h"
 #include "lvk/sst_read.h"
+#include "lvk/stage.h"
 
 namespace lvk {
 
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(kSgThreads) void sg_get(const SgArgs G) {
         r.status = LV_SST_GET_NO_TABLE;
     } else if (seq > LV_MT_MAX_SEQUENCE) {
         r.status = LV_SST_GET_BAD_SEQ;
-    } else if (qo > G.qkeys_bytes || ql > G.qkeys_bytes - qo) {  // u64, no wrap
+    } else if (!extent_ok(qo, ql, G.qkeys_bytes)) {
         r.status = LV_SST_GET_BAD_QUERY;
     } else {
         const lvr::Target t{G.qkeys + qo, ql, (seq << 8) | LV_WB_TYPE_VALUE};
@@ -138,13 +139,6 @@ namespace {
 
 constexpr uint64_t kMaxNq = 0xfffffffeull;
 constexpr uint64_t kMaxBlockCap = 0xfffffffcull;
-
-bool overlaps(const void *a, uint64_t ab, const void *b, uint64_t bb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return ab && bb && x < y + bb && y < x + ab;
-}
-
-bool misaligned(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 
 }  // namespace
 

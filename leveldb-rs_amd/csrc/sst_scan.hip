@@ -33,9 +33,10 @@
 //              key suffix and the value from the block).  A copy of
 //              kSsWaveCopy bytes or more is the wave's: kSsCopyLanes lanes
 //              share it in 16-byte granules of the destination's alignment,
-//              64 / kSsCopyLanes such copies at a time (sst_build.hip's scheme,
-//              with fewer lanes per copy: the values that reach it here are
-//              mostly short, and more of them are then in flight).
+//              64 / kSsCopyLanes such copies at a time (lvk/stage.h's
+//              group_copy, which sst_build.hip uses too, with fewer lanes per
+//              copy: the values that reach it here are mostly short, and more
+//              of them are then in flight).
 //              The lanes of a wave step through their runs together, and a
 //              workgroup-scope fence closes every step: the next entry's
 //              prefix is read from bytes that other lanes of the wave may
@@ -47,6 +48,8 @@
 // The launch sequence depends only on host values (op_cap, block_cap, whether
 // d_order is NULL).  No workgroup waits on another; every loop is bounded by
 // the block it walks.  All sizes and positions are u64.
+// The tile scans, the carries' wave scan and the op loads and stores are
+// lvk/stage.h's too (tile_scan, carry_scan, load_op, store_op).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -58,6 +61,7 @@
 #include "lvh.h"
 #include "lvk/knobs.h"
 #include "lvk/sst_scan.h"
+#include "lvk/stage.h"
 
 namespace lvk {
 
@@ -71,8 +75,6 @@ static_assert(kSsTile % kSsThreads == 0, "a tile is whole rounds of a workgroup"
 static_assert(kSsTile * 16 <= 65536, "two u64 scan arrays fit the LDS a workgroup may declare");
 static_assert(kSsWaveCopy >= 16, "a wave copy has at least one granule");
 static_assert(kSsCopyLanes >= 1 && 64 % kSsCopyLanes == 0, "a wave is whole groups of copy lanes");
-
-typedef uint32_t ss_u4 __attribute__((ext_vector_type(4)));
 
 struct SsHead {  // workspace, every field written by ss_header
     uint32_t st0;  // the bits the header decides: UPSTREAM, NO_TABLE, CORRUPT, BLOCK_OVER
@@ -133,22 +135,6 @@ __global__ void ss_header(const SsArgs A) {
     *A.head = h;
 }
 
-// In-place inclusive scan of s[0, kSsTile).
-__device__ __forceinline__ void ss_tile_scan(uint64_t *s, uint32_t tid) {
-    for (uint32_t off = 1; off < kSsTile; off <<= 1) {
-        uint64_t v[kSsPer];
-#pragma unroll
-        for (uint32_t k = 0; k < kSsPer; ++k) {
-            const uint32_t j = tid + k * kSsThreads;
-            v[k] = j >= off ? s[j - off] : 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t k = 0; k < kSsPer; ++k) s[tid + k * kSsThreads] += v[k];
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(kSsThreads) void ss_blocks(const SsArgs A) {
     __shared__ uint64_t s_r[kSsTile];
     const uint32_t tid = threadIdx.x;
@@ -174,22 +160,13 @@ __global__ __launch_bounds__(kSsThreads) void ss_blocks(const SsArgs A) {
         s_r[j] = v;
     }
     __syncthreads();
-    ss_tile_scan(s_r, tid);
+    tile_scan<kSsTile, kSsThreads>(s_r, 1, tid);
 #pragma unroll
     for (uint32_t k = 0; k < kSsPer; ++k) {
         const uint32_t j = tid + k * kSsThreads;
         if (j < cnt) A.Rl[base + j] = s_r[j];
     }
     if (tid == 0) A.cR[blockIdx.x] = s_r[cnt - 1];
-}
-
-__device__ __forceinline__ uint64_t ss_wave_incl(uint64_t v, uint32_t lane) {
-#pragma unroll
-    for (uint32_t o = 1; o < 64; o <<= 1) {
-        const uint64_t u = __shfl_up(static_cast<unsigned long long>(v), o, 64);
-        if (lane >= o) v += u;
-    }
-    return v;
 }
 
 // The exclusive scan over the tiles of a column, in place; one wave per
@@ -211,14 +188,7 @@ __global__ __launch_bounds__(kSsThreads) void ss_carry(const SsArgs A, uint32_t 
         tiles = (h->runs + kSsTile - 1) / kSsTile;
         if (tiles > A.run_tiles) tiles = A.run_tiles;
     }
-    uint64_t run = 0;
-    for (uint64_t t0 = 0; t0 < tiles; t0 += 64) {  // wave-uniform
-        const uint64_t t = t0 + lane;
-        const uint64_t v = t < tiles ? col[t] : 0;
-        const uint64_t inc = ss_wave_incl(v, lane);
-        if (t < tiles) col[t] = run + inc - v;
-        run += __shfl(static_cast<unsigned long long>(inc), 63, 64);
-    }
+    const uint64_t run = carry_scan(col, 1, tiles, lane);
     if (which == 0 && lane == 0) h->runs = run;
 }
 
@@ -267,8 +237,8 @@ __global__ __launch_bounds__(kSsThreads) void ss_count(const SsArgs A) {
             s_b[j] = b;
         }
         __syncthreads();
-        ss_tile_scan(s_e, tid);
-        ss_tile_scan(s_b, tid);
+        tile_scan<kSsTile, kSsThreads>(s_e, 1, tid);
+        tile_scan<kSsTile, kSsThreads>(s_b, 1, tid);
 #pragma unroll
         for (uint32_t k = 0; k < kSsPer; ++k) {
             const uint32_t j = tid + k * kSsThreads;
@@ -312,67 +282,6 @@ __global__ void ss_plan(const SsArgs A) {
     if (A.mt && st) *A.mt = lv_mt_totals{0, 0, LV_MT_BUILD_UPSTREAM};
 }
 
-// len bytes from src to dst by kSsCopyLanes lanes: dst's ragged head and tail
-// byte by byte, between them 16-byte granules of dst's alignment (an unaligned
-// load, an aligned store).  len >= 16.
-__device__ __forceinline__ void ss_wave_copy(uint8_t *dst, const uint8_t *src, uint64_t len, uint32_t lane) {
-    const uint32_t head = static_cast<uint32_t>((16u - (reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u);
-    const uint64_t gran = (len - head) / 16;
-    const uint32_t tail = static_cast<uint32_t>((len - head) % 16);
-    for (uint32_t i = lane; i < head; i += kSsCopyLanes) dst[i] = src[i];
-    for (uint64_t g = lane; g < gran; g += kSsCopyLanes) {
-        ss_u4 v;
-        __builtin_memcpy(&v, src + head + g * 16, 16);
-        *reinterpret_cast<ss_u4 *>(dst + head + g * 16) = v;
-    }
-    for (uint32_t i = lane; i < tail; i += kSsCopyLanes) dst[head + gran * 16 + i] = src[head + gran * 16 + i];
-}
-
-// A lane's copy job: short ones it does itself, the others its wave does, a
-// group of kSsCopyLanes lanes per job and 64 / kSsCopyLanes jobs at a time.
-// Every lane of the wave calls it.
-__device__ __forceinline__ void ss_copy(uint8_t *dst, const uint8_t *src, uint64_t len, uint32_t lane) {
-    constexpr uint32_t kGroups = 64 / kSsCopyLanes;
-    if (len < kSsWaveCopy)
-        for (uint64_t i = 0; i < len; ++i) dst[i] = src[i];
-    uint64_t todo = __ballot(len >= kSsWaveCopy);
-    const uint32_t grp = lane / kSsCopyLanes;
-    while (todo) {  // wave-uniform
-        int l = -1;  // this group's job: the grp-th lane of todo, if there is one
-        uint64_t t = todo;
-#pragma unroll
-        for (uint32_t k = 0; k < kGroups; ++k) {
-            if (k <= grp) l = t ? __ffsll(static_cast<unsigned long long>(t)) - 1 : -1;
-            t &= t - 1;  // (0 stays 0)
-        }
-        todo = t;
-        const int from = l < 0 ? 0 : l;
-        uint8_t *d = reinterpret_cast<uint8_t *>(__shfl(reinterpret_cast<unsigned long long>(dst), from, 64));
-        const uint8_t *sp = reinterpret_cast<const uint8_t *>(__shfl(reinterpret_cast<unsigned long long>(src), from, 64));
-        const uint64_t m = __shfl(static_cast<unsigned long long>(len), from, 64);
-        if (l >= 0) ss_wave_copy(d, sp, m, lane % kSsCopyLanes);
-    }
-}
-
-__device__ __forceinline__ void ss_store_op(lv_wb_op *p, const lv_wb_op &o) {
-    ss_u4 *q = reinterpret_cast<ss_u4 *>(p);  // d_ops is 16-B aligned, an op is 32 bytes
-    q[0] = ss_u4{static_cast<uint32_t>(o.tag), static_cast<uint32_t>(o.tag >> 32), static_cast<uint32_t>(o.key_off),
-                 static_cast<uint32_t>(o.key_off >> 32)};
-    q[1] = ss_u4{static_cast<uint32_t>(o.val_off), static_cast<uint32_t>(o.val_off >> 32), o.key_len, o.val_len};
-}
-
-__device__ __forceinline__ lv_wb_op ss_load_op(const lv_wb_op *p) {
-    const ss_u4 *q = reinterpret_cast<const ss_u4 *>(p);
-    const ss_u4 a = q[0], b = q[1];
-    lv_wb_op o;
-    o.tag = (static_cast<uint64_t>(a.y) << 32) | a.x;
-    o.key_off = (static_cast<uint64_t>(a.w) << 32) | a.z;
-    o.val_off = (static_cast<uint64_t>(b.y) << 32) | b.x;
-    o.key_len = b.z;
-    o.val_len = b.w;
-    return o;
-}
-
 // Every lane of a wave stays to the end: the long copies are the wave's.
 __global__ __launch_bounds__(kSsThreads) void ss_emit(const SsArgs A) {
     const SsHead *h = A.head;
@@ -402,13 +311,14 @@ __global__ __launch_bounds__(kSsThreads) void ss_emit(const SsArgs A) {
             lv_wb_op op;
             if (lvs::step(raw, &w, &e)) {  // (ss_count accepted the run)
                 koff = lvs::emit_entry(raw, e, w.klen, A.arena, koff, &p, &op, jobs);
-                ss_store_op(A.ops + ei++, op);
+                store_op(A.ops + ei++, op);
             } else {
                 w.at = w.end;  // (an image that changed under the call: the loop still ends)
             }
         }
 #pragma unroll
-        for (uint32_t j = 0; j < 3; ++j) ss_copy(jobs[j].dst, jobs[j].src, jobs[j].len, lane);
+        for (uint32_t j = 0; j < 3; ++j)
+            group_copy<kSsCopyLanes, kSsWaveCopy>(jobs[j].dst, jobs[j].src, jobs[j].len, lane);
         __threadfence_block();  // the next entry's prefix: bytes this wave's lanes have just stored
     }
 }
@@ -423,7 +333,7 @@ __global__ __launch_bounds__(kSsThreads) void ss_order(const SsArgs A) {
         fresh = i == 0;
         if (i) {
             bool same;
-            bad = lvs::op_compare(A.arena, ss_load_op(A.ops + i - 1), ss_load_op(A.ops + i), &same) > 0;
+            bad = lvs::op_compare(A.arena, load_op(A.ops + i - 1), load_op(A.ops + i), &same) > 0;
             fresh = !same;
         }
     }
@@ -449,47 +359,34 @@ namespace {
 constexpr uint64_t kMaxOpCap = 0xfffffffeull;
 constexpr uint64_t kMaxBlockCap = 0xfffffffcull;
 
-struct SsWs {
-    size_t head, boff, bsize, Rl, cR, El, Bl, cE, cB, total;
-    uint64_t btiles, run_cap, rtiles;
-};
-SsWs ss_ws_layout(uint64_t op_cap, uint64_t bc) {
-    SsWs w;
-    w.btiles = (bc + lvk::kSsTile - 1) / lvk::kSsTile;
-    w.run_cap = bc ? op_cap + bc : 0;  // a run but an empty block's holds an entry; no block, no run
-    w.rtiles = (w.run_cap + lvk::kSsTile - 1) / lvk::kSsTile;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += al16(bytes);
-        return o;
-    };
-    w.head = take(sizeof(lvk::SsHead));
-    w.boff = take(bc * 8);
-    w.bsize = take(bc * 8);
-    w.Rl = take(bc * 8);
-    w.cR = take(w.btiles * 8);
-    w.El = take(w.run_cap * 8);
-    w.Bl = take(w.run_cap * 8);
-    w.cE = take(w.rtiles * 8);
-    w.cB = take(w.rtiles * 8);
-    w.total = at;
-    return w;
+// The workspace for op_cap and block_cap = bc, region by region: fills A's
+// run_cap, run_tiles and workspace pointers; returns the block tiles.
+uint64_t ss_carve(Carve &C, uint64_t op_cap, uint64_t bc, lvk::SsArgs &A) {
+    const uint64_t btiles = (bc + lvk::kSsTile - 1) / lvk::kSsTile;
+    A.run_cap = bc ? op_cap + bc : 0;  // a run but an empty block's holds an entry; no block, no run
+    A.run_tiles = (A.run_cap + lvk::kSsTile - 1) / lvk::kSsTile;
+    A.head = C.take<lvk::SsHead>(1);
+    A.boff = C.take<uint64_t>(bc);
+    A.bsize = C.take<uint64_t>(bc);
+    A.Rl = C.take<uint64_t>(bc);
+    A.cR = C.take<uint64_t>(btiles);
+    A.El = C.take<uint64_t>(A.run_cap);
+    A.Bl = C.take<uint64_t>(A.run_cap);
+    A.cE = C.take<uint64_t>(A.run_tiles);
+    A.cB = C.take<uint64_t>(A.run_tiles);
+    return btiles;
 }
-
-bool overlaps(const void *a, uint64_t ab, const void *b, uint64_t bb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return ab && bb && x < y + bb && y < x + ab;
-}
-
-bool misaligned(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 
 }  // namespace
 
 extern "C" {
 
 size_t lv_sst_scan_workspace_bytes(size_t op_cap, size_t block_cap) {
-    return (op_cap > kMaxOpCap || block_cap > kMaxBlockCap) ? 0 : ss_ws_layout(op_cap, block_cap).total;
+    if (op_cap > kMaxOpCap || block_cap > kMaxBlockCap) return 0;
+    lvk::SsArgs A{};
+    Carve C{nullptr};
+    ss_carve(C, op_cap, block_cap, A);
+    return C.at;
 }
 
 int lv_sst_scan_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_table *d_table,
@@ -517,8 +414,10 @@ int lv_sst_scan_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_ta
     if (misaligned(d_ops, 16)) return set_err(LV_ERR_INVALID, "d_ops must be 16-byte aligned");
     if (!d_workspace) return set_err(LV_ERR_INVALID, "null workspace");
     if (misaligned(d_workspace, 16)) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
-    const SsWs ws = ss_ws_layout(op_cap, block_cap);
-    if (workspace_bytes < ws.total) return set_err(LV_ERR_INVALID, "workspace too small");
+    lvk::SsArgs A{};
+    Carve C{static_cast<uint8_t *>(d_workspace)};
+    const uint64_t btiles = ss_carve(C, op_cap, block_cap, A);
+    if (workspace_bytes < C.at) return set_err(LV_ERR_INVALID, "workspace too small");
     const struct {
         const void *p;
         uint64_t bytes;
@@ -534,9 +433,7 @@ int lv_sst_scan_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_ta
     DevCtx *c = nullptr;
     if (int rc = current_ctx(&c)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *wb = static_cast<uint8_t *>(d_workspace);
 
-    lvk::SsArgs A{};
     A.file = d_file;
     A.file_cap = file_cap;
     A.table = d_table;
@@ -546,33 +443,22 @@ int lv_sst_scan_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_ta
     A.ops = d_ops;
     A.op_cap = op_cap;
     A.block_cap = block_cap;
-    A.run_cap = ws.run_cap;
-    A.run_tiles = ws.rtiles;
     A.order = d_order;
     A.mt = d_mt_totals;
     A.totals = d_totals;
-    A.head = reinterpret_cast<lvk::SsHead *>(wb + ws.head);
-    A.boff = reinterpret_cast<uint64_t *>(wb + ws.boff);
-    A.bsize = reinterpret_cast<uint64_t *>(wb + ws.bsize);
-    A.Rl = reinterpret_cast<uint64_t *>(wb + ws.Rl);
-    A.cR = reinterpret_cast<uint64_t *>(wb + ws.cR);
-    A.El = reinterpret_cast<uint64_t *>(wb + ws.El);
-    A.Bl = reinterpret_cast<uint64_t *>(wb + ws.Bl);
-    A.cE = reinterpret_cast<uint64_t *>(wb + ws.cE);
-    A.cB = reinterpret_cast<uint64_t *>(wb + ws.cB);
 
     const dim3 b(lvk::kSsThreads);
     hipLaunchKernelGGL(lvk::ss_header, dim3(1), dim3(1), 0, s, A);
     if (block_cap) {  // (no block: a table with entries is BLOCK_OVER)
-        hipLaunchKernelGGL(lvk::ss_blocks, dim3(static_cast<uint32_t>(ws.btiles)), b, 0, s, A);
+        hipLaunchKernelGGL(lvk::ss_blocks, dim3(static_cast<uint32_t>(btiles)), b, 0, s, A);
         hipLaunchKernelGGL(lvk::ss_carry, dim3(1), b, 0, s, A, 0u);
-        hipLaunchKernelGGL(lvk::ss_count, dim3(static_cast<uint32_t>(std::min<uint64_t>(ws.rtiles, lvk::kSsMaxGrid))), b, 0,
+        hipLaunchKernelGGL(lvk::ss_count, dim3(static_cast<uint32_t>(std::min<uint64_t>(A.run_tiles, lvk::kSsMaxGrid))), b, 0,
                            s, A);
         hipLaunchKernelGGL(lvk::ss_carry, dim3(1), b, 0, s, A, 1u);
     }
     hipLaunchKernelGGL(lvk::ss_plan, dim3(1), dim3(1), 0, s, A);
     if (block_cap && op_cap) {
-        const uint64_t eg = (ws.run_cap + lvk::kSsThreads - 1) / lvk::kSsThreads;
+        const uint64_t eg = (A.run_cap + lvk::kSsThreads - 1) / lvk::kSsThreads;
         hipLaunchKernelGGL(lvk::ss_emit, dim3(static_cast<uint32_t>(eg)), b, 0, s, A);
     }
     if (d_order) {

@@ -1,0 +1,77 @@
+"""The workspace sizes of the four pipeline stages that take one, pinned.
+
+A caller sizes its buffer with lv_*_workspace_bytes and the device entry point
+cuts the same buffer into regions, so the numbers are part of what a caller
+sees: a region that moves or grows changes them.  The expected values are
+literals.  They were taken from the library as it was before each stage's
+workspace came to be described once (one function that carves the regions,
+run without a buffer to measure): that commit was built and these functions
+called on it; they need no GPU.  Capacities lie either side of each stage's
+tile (256 records, 512 and 1,024 entries, 1,024 blocks), and one lies beyond
+each documented limit."""
+import pytest
+
+import lvgpu.memtable as MT
+import lvgpu.table as T
+import lvgpu.write_batch as WB
+
+CAPS = (0, 1, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 100000)
+BLOCK_CAPS = (0, 1, 1024, 1025)
+MAX_CAP = 2**32 - 2        # op_cap / rec_cap of one call
+MAX_BLOCK_CAP = 2**32 - 4  # block_cap of one call
+
+WB_DECODE = (64, 112, 3152, 3152, 3184, 6224, 6224, 6272, 12384, 12384, 12432, 1203200)
+MT_BUILD = (16, 80, 16336, 16400, 16464, 32720, 32784, 32848, 65488, 65552, 65616, 6400016)
+# rows: op_cap in CAPS; columns: block_cap in BLOCK_CAPS
+SST_BUILD = (
+    (2100480, 2100512, 2120960, 2120992),
+    (2108896, 2108928, 2129376, 2129408),
+    (2124352, 2124384, 2144832, 2144864),
+    (2124352, 2124384, 2144832, 2144864),
+    (2124512, 2124544, 2144992, 2145024),
+    (2139968, 2140000, 2160448, 2160480),
+    (2139968, 2140000, 2160448, 2160480),
+    (2140128, 2140160, 2160608, 2160640),
+    (2171200, 2171232, 2191680, 2191712),
+    (2171200, 2171232, 2191680, 2191712),
+    (2179552, 2179584, 2200032, 2200064),
+    (9006432, 9006464, 9026912, 9026944),
+)
+SST_SCAN = (
+    (112, 240, 41120, 41200),
+    (112, 240, 41152, 41200),
+    (112, 4304, 45216, 45264),
+    (112, 4336, 45216, 45296),
+    (112, 4336, 45248, 45296),
+    (112, 8400, 49312, 49360),
+    (112, 8432, 49312, 49392),
+    (112, 8432, 49344, 49392),
+    (112, 16592, 57504, 57552),
+    (112, 16624, 57504, 57616),
+    (112, 16624, 57568, 57616),
+    (112, 1601776, 1642688, 1642768),
+)
+
+
+def test_write_batch_decode_workspace_bytes():
+    assert tuple(WB.decode_workspace_bytes(c) for c in CAPS) == WB_DECODE
+    # the size function knows no limit (lv_write_batch_decode_device refuses rec_cap > 2^32 - 2)
+    assert WB.decode_workspace_bytes(MAX_CAP) == 51673825328
+    assert WB.decode_workspace_bytes(MAX_CAP + 1) == 51673825344
+
+
+def test_memtable_build_workspace_bytes():
+    assert tuple(MT.build_workspace_bytes(c) for c in CAPS) == MT_BUILD
+    assert MT.build_workspace_bytes(MAX_CAP) == 274877906832
+    assert MT.build_workspace_bytes(MAX_CAP + 1) == 0
+
+
+@pytest.mark.parametrize("fn, want, at_limit", [(T.build_workspace_bytes, SST_BUILD, 382388407376),
+                                                 (T.scan_workspace_bytes, SST_SCAN, 240685940656)],
+                         ids=["sst_build", "sst_scan"])
+def test_sst_workspace_bytes(fn, want, at_limit):
+    assert tuple(tuple(fn(c, b) for b in BLOCK_CAPS) for c in CAPS) == want
+    assert fn(MAX_CAP, MAX_BLOCK_CAP) == at_limit
+    assert fn(MAX_CAP + 1, 0) == 0
+    assert fn(0, MAX_BLOCK_CAP + 1) == 0
+    assert fn(MAX_CAP + 1, MAX_BLOCK_CAP + 1) == 0
