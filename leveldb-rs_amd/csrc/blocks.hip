@@ -32,7 +32,9 @@ __global__ __launch_bounds__(kThreads) void crc32c_batch_kernel(Params P, const 
 // multiple of 16*G*U, so every block is `nb` whole batches and every group
 // of a wave walks the same (block round, batch) sequence: the batch control
 // is wave-uniform (scalar), there is no head/tail work, and the seed enters
-// as lane 0's first word.
+// as lane 0's first word.  Every row ends on the block's last batch, so the
+// rows' registers are carried from batch to batch through the jump table of
+// the blocks images (fold_batch_carry; `last` = the block's last batch).
 // Every step issues the SAME loads (next batch, and for seeded calls the
 // next block's seed) whether or not a next batch exists -- the last one
 // reads the arena's first row.  The compiler's s_waitcnt counts are static:
@@ -184,12 +186,12 @@ __global__ __launch_bounds__(kThreads) void crc32c_blocks_kernel(Params P, uint3
                 v3[i] = load16(ptr + kBatch * (nb > 3 ? 3u : 0u) + kRow * i);
             }
             const Lut L = make_lut(lane);
-            uint32_t A[U];
+            uint32_t A[U] = {};
             if (gl == 0) slot0[0].x ^= kVarS0 ? seed_ld(blk) : 0xffffffffu;
-            fold_batch<true>(slot0, A, L);
-            if (nb > 1) fold_batch<false>(v1, A, L);
-            if (nb > 2) fold_batch<false>(v2, A, L);
-            if (nb > 3) fold_batch<false>(v3, A, L);
+            fold_batch_carry(slot0, A, L, nb == 1);
+            if (nb > 1) fold_batch_carry(v1, A, L, nb == 2);
+            if (nb > 2) fold_batch_carry(v2, A, L, nb == 3);
+            if (nb > 3) fold_batch_carry(v3, A, L, nb == 4);
             const uint32_t X = merge_group<G, -1, -1, true>(A, L);
             if constexpr (FUSE) {
                 if (gl == 0) g_ocrc[wave][lane / G] = X;
@@ -214,7 +216,7 @@ __global__ __launch_bounds__(kThreads) void crc32c_blocks_kernel(Params P, uint3
     if (G == 16 && nb >= 8 && rounds * nb >= 64)
         for (uint32_t k = 0; k < wave * LVK_STAGGER; ++k) __builtin_amdgcn_s_sleep(32);
     const Lut L = make_lut(lane);
-    uint32_t A[U];
+    uint32_t A[U] = {};  // the rows' carried registers: 0 at a block's first batch
     // The flush store's operands live in registers of their own for the whole
     // loop (kept live past it below), so no loop temporary reuses them: a
     // write to a pending store's source register waits for the store, i.e.
@@ -235,16 +237,14 @@ __global__ __launch_bounds__(kThreads) void crc32c_blocks_kernel(Params P, uint3
         if constexpr (kVarS0) s0n = seed_ld(blk + gstride);
 #pragma unroll
         for (uint32_t i = 0; i < U; ++i) nxt[i] = load16(lptr + kRow * i);
-        if (j == 0) {
-            if (gl == 0) cur[0].x ^= s0;
-            fold_batch<true>(cur, A, L);
-        } else {
-            fold_batch<false>(cur, A, L);
-        }
+        if (j == 0 && gl == 0) cur[0].x ^= s0;
+        fold_batch_carry(cur, A, L, lastj);
         if (lastj) {
             // round r's K results -> LDS slot (r % G)*K + group; one store of
             // the wave's 64 slots every G rounds (and after the last round)
             const uint32_t X = merge_group<G, -1, -1, true>(A, L);
+#pragma unroll
+            for (uint32_t i = 0; i < U; ++i) A[i] = 0u;
             if (gl == 0) g_ocrc[wave][(r % G) * kGroups + lane / G] = PIECES ? X : final_crc(P, X);
             if (!FUSE && ((r + 1) % G == 0 || r + 1 == rounds)) {
                 __builtin_amdgcn_wave_barrier();
@@ -473,12 +473,13 @@ void launch_blocks_g(const DevCtx &c, int gi, const uint8_t *base, uint64_t stri
     const uint32_t nb = static_cast<uint32_t>(blen / (16ull * G * lvk::U));
     static const std::string name = "crc32c_blocks_kernel<" + std::to_string(G) + (GATHER ? ",gather>" : ">");
     g_kernel = name.c_str();
+    const uint4 *image = c.image[kBlocksImage + gi];  // region A's second half: the carried fold's jump table
     if (seed)
         hipLaunchKernelGGL((lvk::crc32c_blocks_kernel<G, true, false, false, GATHER>),
-                           dim3(static_cast<uint32_t>(grid)), dim3(lvk::kThreads), 0, s, P, nb, c.image[gi]);
+                           dim3(static_cast<uint32_t>(grid)), dim3(lvk::kThreads), 0, s, P, nb, image);
     else
         hipLaunchKernelGGL((lvk::crc32c_blocks_kernel<G, false, false, false, GATHER>),
-                           dim3(static_cast<uint32_t>(grid)), dim3(lvk::kThreads), 0, s, P, nb, c.image[gi]);
+                           dim3(static_cast<uint32_t>(grid)), dim3(lvk::kThreads), 0, s, P, nb, image);
 }
 
 template <bool GATHER>
@@ -514,15 +515,16 @@ void launch_pieces(DevCtx &c, uint32_t ps, const uint32_t *mats, const uint32_t 
     P.pshift = ps;
     P.mats = mats;
     set_hint(P, hc, blen);
+    const uint4 *image = c.image[kBlocksImage + 2];
     if (!scr) {  // one round of the grid: each workgroup joins its own blocks' pieces
         P.out = out;
         const dim3 grid(static_cast<uint32_t>((nv + 63) / 64));
         if (seed)
             hipLaunchKernelGGL((lvk::crc32c_blocks_kernel<16, true, true, true, GATHER>), grid, dim3(lvk::kThreads), 0,
-                               hs, P, nb, c.image[2]);
+                               hs, P, nb, image);
         else
             hipLaunchKernelGGL((lvk::crc32c_blocks_kernel<16, false, true, true, GATHER>), grid, dim3(lvk::kThreads),
-                               0, hs, P, nb, c.image[2]);
+                               0, hs, P, nb, image);
         g_kernel = GATHER ? "crc32c_blocks_kernel<16,pieces,fused,gather>" : "crc32c_blocks_kernel<16,pieces,fused>";
         return;
     }
@@ -530,10 +532,10 @@ void launch_pieces(DevCtx &c, uint32_t ps, const uint32_t *mats, const uint32_t 
     const uint64_t grid = std::min<uint64_t>(c.cus, (nv + 63) / 64);
     if (seed)
         hipLaunchKernelGGL((lvk::crc32c_blocks_kernel<16, true, true, false, GATHER>), dim3(static_cast<uint32_t>(grid)),
-                           dim3(lvk::kThreads), 0, hs, P, nb, c.image[2]);
+                           dim3(lvk::kThreads), 0, hs, P, nb, image);
     else
         hipLaunchKernelGGL((lvk::crc32c_blocks_kernel<16, false, true, false, GATHER>),
-                           dim3(static_cast<uint32_t>(grid)), dim3(lvk::kThreads), 0, hs, P, nb, c.image[2]);
+                           dim3(static_cast<uint32_t>(grid)), dim3(lvk::kThreads), 0, hs, P, nb, image);
     if (ps >= 11) {  // > 1,024 pieces per block: a workgroup per block
         hipLaunchKernelGGL(lvk::combine_pieces_wg_kernel, dim3(static_cast<uint32_t>(n)), dim3(1024), 0, hs, P.out,
                            1u << ps, tabs, out, flags);

@@ -85,6 +85,15 @@ const std::vector<uint32_t> &host_image(int gi) {
         for (int e = 0; e < 256; ++e)
             for (int c = 0; c < 8; ++c)
                 for (int k = 0; k < 4; ++k) ra[e * 64 + 32 + 4 * c + k] = WT[3 - k][e];
+        for (int i = 0; i < 4; ++i) {
+            uint32_t J[4][256];
+            lvgpu::shift_tables(16ull * kGs[i] * lvk::U - 12, J);
+            images[kBlocksImage + i] = images[i];
+            uint32_t *rj = &images[kBlocksImage + i][lvk::kRegionA / 4];
+            for (int e = 0; e < 256; ++e)
+                for (int c = 0; c < 8; ++c)
+                    for (int k = 0; k < 4; ++k) rj[e * 64 + 32 + 4 * c + k] = J[3 - k][e];
+        }
     });
     return images[gi];
 }

@@ -45,10 +45,14 @@ constexpr int kTableImage = 4;
 constexpr uint32_t kAlRowsH = LVK_AL_ROWS;  // = lvk::kAlRows (lvk/sort.h)
 constexpr int kAlImage = kAlRowsH == 4 ? 2 : kTableImage;
 static_assert(kAlRowsH == 4 || kAlRowsH == lvk::kSstRows, "aligned rows: 4, or the table image's");
-constexpr int kImages = 5;
+// The uniform-block kernel's images, one per G (kBlocksImage + index into
+// kGs): the per-G image with region A's row shift replaced by the carried
+// fold's jump Shift_{16*G*U - 12} (lvk::fold_batch_carry).
+constexpr int kBlocksImage = 5;
+constexpr int kImages = 9;
 
-// Host copy of the LDS image for each G (index into kGs), and the table
-// image; layout in lvk/core.h.
+// Host copy of the LDS image for each G (index into kGs), the table image
+// and the blocks images; layout in lvk/core.h.
 const std::vector<uint32_t> &host_image(int gi);
 
 // Library-owned sort workspace of one (device, stream).  Calls on one stream
@@ -72,7 +76,7 @@ struct DevCtx {
     std::mutex m;  // one-time init
     bool ready = false;
     int cus = 0;
-    uint4 *image[kImages] = {};  // per G (kGs), then the table image
+    uint4 *image[kImages] = {};  // per G (kGs), the table image, the blocks images per G
     uint32_t *base_tabs = nullptr;  // Shift_{2^i}, i < lvk::kBaseMats, as byte tables (4 x 256 words each)
     std::mutex ws_m;  // guards the map (entries are never erased)
     std::map<hipStream_t, std::unique_ptr<StreamWs>> ws;

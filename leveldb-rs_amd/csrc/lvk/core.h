@@ -18,7 +18,11 @@
 //    U rows A_i = Shift_{16GU}(A_i) ^ p_i (Horner), then the rows merge and
 //    the lanes combine pairwise, X_l = Shift_{16*2^k}(X_l) ^ X_{l+2^k},
 //    k < log2 G.  The < 16 bytes after the last whole granule fold in as one
-//    shifted granule (fold_tail).
+//    shifted granule (fold_tail).  The uniform-block kernel, whose rows all
+//    end on a block's last batch, carries A_i instead (fold_batch_carry): the
+//    last slice step of a granule reads J = Shift_{16GU-12} in place of
+//    T = Shift_4 and the result enters the next batch's first word, so the
+//    row shift costs no lookup of its own.
 //  * The seed enters by xoring (seed ^ ~0) into the first 4 buffer bytes:
 //    R(s, w||D) = R(0, (s^w)||D).  Buffers shorter than 4 bytes go bytewise.
 //  * Lookup tables live in LDS.  The slice tables T0..T3 and the row-shift
@@ -49,7 +53,8 @@ constexpr uint32_t U = 4;       // rows per batch (= interleaved Horner accumula
 
 // LDS image (bytes):
 //   [0, 64K)      region A, 256 rows x 256 B: dwords 0..31 T0..T3 (Latin),
-//                 dwords 32..63 W4 = Shift_{16*G*U} (Latin)
+//                 dwords 32..63 W4 = Shift_{16*G*U} (Latin); the blocks
+//                 kernel's images hold J = Shift_{16*G*U - 12} there
 //   [64K, 128K)   region B: dwords 0..31 W1 = Shift_{16*G}, 32..63 W2 = Shift_{32*G}
 //   [128K, 152K)  combine tables Shift_{16*2^k}, k = 0..5, plain byte tables
 constexpr uint32_t kRegionA = 0;
@@ -227,6 +232,52 @@ __device__ __forceinline__ void fold_batch(const uint4 (&v)[NU], uint32_t (&A)[N
     }
 }
 
+// The carried fold of the uniform-block kernel (blocks image, region A's
+// second half J = Shift_{16*G*NU - 12}).  Row i of a lane is one CRC stream
+// over its granules of successive batches, 16*G*NU bytes apart: A[i] enters
+// as the register just before this batch's granule (xored into its first
+// word; 0 at a block's first batch) and leaves as the register just before
+// the next batch's -- the last slice step reads J instead of T = Shift_4, so
+// the row shift costs no lookup of its own -- or, on the block's LAST batch
+// (T), as R at the end of the granule, which is what merge_group takes.
+// `last` is wave-uniform.  J sits kHalf bytes after T in every row and the
+// lane's dword offsets are < kHalf, so the J address is the T address with
+// bit 7 of the offset byte set: one select per batch, no second body.
+template <uint32_t NU = U>
+__device__ __forceinline__ void fold_batch_carry(const uint4 (&v)[NU], uint32_t (&A)[NU], const Lut &L, bool last) {
+    Lut L3 = L;
+    L3.lv = last ? L.lv : L.lv | 0x80808080u;
+    uint32_t s[NU];
+#pragma unroll
+    for (uint32_t i = 0; i < NU; ++i) s[i] = v[i].x ^ A[i];
+#pragma unroll
+    for (uint32_t step = 0; step < 4; ++step) {
+        const Lut &Ls = step < 3 ? L : L3;
+        uint32_t ad[NU][4];
+#pragma unroll
+        for (uint32_t i = 0; i < NU; ++i) {
+            ad[i][0] = lut_addr<0>(s[i], Ls);
+            ad[i][1] = lut_addr<1>(s[i], Ls);
+            ad[i][2] = lut_addr<2>(s[i], Ls);
+            ad[i][3] = lut_addr<3>(s[i], Ls);
+        }
+        uint32_t t[NU][4];
+#pragma unroll
+        for (uint32_t i = 0; i < NU; ++i)
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) t[i][k] = lds_word(ad[i][k] + kRegionA);
+#pragma unroll
+        for (uint32_t i = 0; i < NU; ++i) {
+            const uint32_t x = xor3(t[i][0], t[i][1], t[i][2]);
+            if (step < 3) {
+                const uint32_t nw = step == 0 ? v[i].y : step == 1 ? v[i].z : v[i].w;
+                s[i] = xor3(x, t[i][3], nw);
+            } else {
+                A[i] = x ^ t[i][3];
+            }
+        }
+    }
+}
 
 // One byte through T0 (this lane's copy): crc32c.rs:81.
 __device__ __forceinline__ uint32_t byte_step(uint32_t s, uint32_t b) {
