@@ -16,15 +16,13 @@
 #include "lv_internal.h"
 #include "lvh.h"
 #include "lvk/sort.h"
+#include "lvk/wal.h"
 
 namespace lvk {
 
 constexpr uint32_t kDecThreads = 256;
 constexpr uint32_t kDecPer = 4;                            // entries per thread
 constexpr uint32_t kDecTile = kDecThreads * kDecPer;       // entries per scan tile
-constexpr uint32_t kDecBlock = 32768;                      // log_format.rs:63
-constexpr uint32_t kDecHeader = 7;                         // log_format.rs:66
-constexpr uint32_t kDecMaxFrags = kDecBlock / kDecHeader + 1;  // headers that fit one block
 constexpr uint64_t kDecNone = ~0ull;
 
 // What a scan entry is to the Reader.  SKIP: never reached (after its block's
@@ -180,69 +178,40 @@ __device__ __forceinline__ void dec_accumulate(DecSum *a, const DecVal &v) {
     a->drop += v.rb[0] + v.rb[1];
 }
 
-// Workgroup scans over LDS (Hillis-Steele, kDecThreads values); the exclusive
-// prefix is returned and *total gets the composite of all.  The tiles are few
-// against the copy's bytes, so the two barriers per step do not show.
-__device__ __forceinline__ DecOp dec_scan_op(DecOp v, DecOp *lds, DecOp *total) {
-    const uint32_t t = threadIdx.x;
+// The workgroup scan over LDS (Hillis-Steele, kDecThreads values of T in
+// lds): each thread gets the composite of the values of the threads before
+// it, the identity where there are none, and *total the composite of all;
+// then(a, b) is "a, then b".  With kBack the threads are taken in reverse: a
+// thread gets the composite of those after it, the last thread's value first.
+// The identity of every scan here is the zero value T{} (dec_ident(), no sums,
+// no event); handed in as an argument it cost wal_dec_tiles and wal_dec_apply
+// some 30 instructions each.  It ends with a barrier, so lds can be reused at
+// once.  The tiles are few against the copy's bytes, so the two barriers per
+// step do not show.
+template <bool kBack, class T, class F>
+__device__ __forceinline__ T dec_scan(T v, T *lds, T *total, F then) {
+    const uint32_t t = kBack ? kDecThreads - 1 - threadIdx.x : threadIdx.x;
     lds[t] = v;
     __syncthreads();
     for (uint32_t d = 1; d < kDecThreads; d <<= 1) {
-        DecOp o = dec_ident();
+        T o{};
         if (t >= d) o = lds[t - d];
         __syncthreads();
         if (t >= d) {
-            v = dec_compose(o, v);
+            v = then(o, v);
             lds[t] = v;
         }
         __syncthreads();
     }
-    const DecOp ex = t ? lds[t - 1] : dec_ident();
+    const T ex = t ? lds[t - 1] : T{};
     *total = lds[kDecThreads - 1];
     __syncthreads();
     return ex;
 }
-
-__device__ __forceinline__ DecSum dec_scan_sum(DecSum v, DecSum *lds, DecSum *total) {
-    const uint32_t t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < kDecThreads; d <<= 1) {
-        DecSum o{0, 0, 0, 0};
-        if (t >= d) o = lds[t - d];
-        __syncthreads();
-        if (t >= d) {
-            v = dec_add(o, v);
-            lds[t] = v;
-        }
-        __syncthreads();
-    }
-    const DecSum ex = t ? lds[t - 1] : DecSum{0, 0, 0, 0};
-    *total = lds[kDecThreads - 1];
-    __syncthreads();
-    return ex;
-}
-
-// For each thread the first non-zero value of the threads after it (0: none);
-// *all gets the first non-zero value of the whole workgroup.
-__device__ __forceinline__ uint32_t dec_next_nonzero(uint32_t v, uint32_t *lds, uint32_t *all) {
-    const uint32_t t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < kDecThreads; d <<= 1) {
-        const uint32_t o = t + d < kDecThreads ? lds[t + d] : 0u;
-        __syncthreads();
-        if (!v) {
-            v = o;
-            lds[t] = v;
-        }
-        __syncthreads();
-    }
-    const uint32_t ex = t + 1 < kDecThreads ? lds[t + 1] : 0u;
-    *all = lds[0];
-    __syncthreads();
-    return ex;
-}
+// Under this, backward, a thread gets the first non-zero value of the threads
+// after it (0: none) and *total the first of the whole workgroup: the nearer
+// value is the later one.
+__device__ __forceinline__ uint32_t dec_nearer(uint32_t farther, uint32_t nearer) { return nearer ? nearer : farther; }
 
 // What a tile of kDecTile entries does, as far as it can be said without the
 // state it starts in.  The incoming state matters only up to the tile's first
@@ -295,16 +264,16 @@ __device__ __forceinline__ uint64_t dec_count(const DecArgs &A) {
 __global__ __launch_bounds__(kDecThreads) void wal_dec_classify(const DecArgs A) {
     const uint64_t n = dec_count(A);
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kDecThreads;
-    const uint64_t eof_blk = A.bytes % kDecBlock ? A.bytes / kDecBlock : kDecNone;
+    const uint64_t eof_blk = A.bytes % kWalBlock ? A.bytes / kWalBlock : kDecNone;
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kDecThreads + threadIdx.x; i < n; i += stride) {
         const uint64_t hdr = A.hdr_off[i];
         const uint32_t info = A.info[i];
         const uint32_t type = info & 0xffu, status = (info >> 8) & 0xffu, len = info >> 16;
-        const uint64_t blk = hdr / kDecBlock;
+        const uint64_t blk = hdr / kWalBlock;
         uint32_t code = kEvSkip, x = 0;
         bool kill = false;
-        if (blk < A.nb && hdr + kDecHeader <= A.bytes) {
-            const uint64_t end = (blk + 1) * kDecBlock < A.bytes ? (blk + 1) * kDecBlock : A.bytes;
+        if (blk < A.nb && hdr + kWalHeader <= A.bytes) {
+            const uint64_t end = (blk + 1) * kWalBlock < A.bytes ? (blk + 1) * kWalBlock : A.bytes;
             const uint32_t left = static_cast<uint32_t>(end - hdr);
             if (status == LV_WAL_REC_BAD_LENGTH) {  // log_reader.rs:312-324
                 code = blk == eof_blk ? kEvEof : kEvBadLen;
@@ -313,15 +282,10 @@ __global__ __launch_bounds__(kDecThreads) void wal_dec_classify(const DecArgs A)
             } else if (status == LV_WAL_REC_ZERO) {  // log_reader.rs:326-331
                 code = kEvBadZero;
                 kill = true;
-            } else if (status == LV_WAL_REC_OK && kDecHeader + len <= left) {
+            } else if (status == LV_WAL_REC_OK && kWalHeader + len <= left) {
                 bool ok = true;
-                if (A.crc) {  // log_reader.rs:335-342
-                    const uint8_t *h = A.log + hdr;
-                    const uint32_t stored = h[0] | (static_cast<uint32_t>(h[1]) << 8) |
-                                            (static_cast<uint32_t>(h[2]) << 16) | (static_cast<uint32_t>(h[3]) << 24);
-                    const uint32_t rot = stored - 0xa282ead8u;  // crc32c.rs:59-63
-                    ok = ((rot >> 17) | (rot << 15)) == A.crc[i];
-                }
+                if (A.crc)  // log_reader.rs:335-342
+                    ok = stored_crc(A.log + hdr) == A.crc[i];
                 if (!ok) {
                     code = kEvBadCrc;
                     x = left;
@@ -335,8 +299,8 @@ __global__ __launch_bounds__(kDecThreads) void wal_dec_classify(const DecArgs A)
             }
             if (code != kEvSkip) {
                 if (kill) atomicMin(&A.fkill[blk], static_cast<uint32_t>(i));
-                if (i == 0 || A.hdr_off[i - 1] / kDecBlock != blk) A.bfirst[blk] = static_cast<uint32_t>(i);
-                if (i + 1 == n || A.hdr_off[i + 1] / kDecBlock != blk) A.bend[blk] = static_cast<uint32_t>(i + 1);
+                if (i == 0 || A.hdr_off[i - 1] / kWalBlock != blk) A.bfirst[blk] = static_cast<uint32_t>(i);
+                if (i + 1 == n || A.hdr_off[i + 1] / kWalBlock != blk) A.bend[blk] = static_cast<uint32_t>(i + 1);
             }
         }
         A.ev[i] = code | (x << 8);
@@ -353,7 +317,7 @@ __device__ __forceinline__ void dec_load(const DecArgs &A, uint64_t i, uint64_t 
     const uint32_t e = A.ev[i];
     if ((e & 0xffu) == kEvSkip) return;
     const uint64_t h = A.hdr_off[i];
-    if (i > A.fkill[h / kDecBlock]) return;
+    if (i > A.fkill[h / kWalBlock]) return;
     *code = e & 0xffu;
     *x = e >> 8;
     *hdr = h;
@@ -383,8 +347,8 @@ __global__ __launch_bounds__(kDecThreads) void wal_dec_reduce(const DecArgs A) {
             dec_load(A, tile * kDecTile + t * kDecPer + j, n, &code[j], &x[j], &hdr[j]);
             loc = dec_compose(loc, dec_event_op(code[j], x[j], hdr[j]));
         }
-        DecOp total;
-        DecOp s = dec_scan_op(loc, s_op, &total);  // (its first barrier orders the zeroing above)
+        DecOp total;  // (the scan's first barrier orders the zeroing above)
+        DecOp s = dec_scan<false>(loc, s_op, &total, dec_compose);
         bool known = (s.flags & kOpConst) != 0;
         DecSum sum{0, 0, 0, 0};
         uint64_t pre_n = 0, pre_k = 0;
@@ -449,7 +413,7 @@ __global__ __launch_bounds__(kDecThreads) void wal_dec_tiles(const DecArgs A) {
         DecTileSum ts{};
         if (tile < ntiles) ts = A.tsum[tile];
         DecOp total;
-        const DecOp ex = dec_scan_op(ts.op, s_op, &total);
+        const DecOp ex = dec_scan<false>(ts.op, s_op, &total, dec_compose);
         DecOp st = dec_compose(carry, ex);  // the state the tile starts in
         const DecOp st_in = st;
         DecSum v = ts.sums;
@@ -468,7 +432,7 @@ __global__ __launch_bounds__(kDecThreads) void wal_dec_tiles(const DecArgs A) {
             dec_accumulate(&v, fv);
         }
         DecSum vtotal;
-        const DecSum vex = dec_scan_sum(v, s_sum, &vtotal);
+        const DecSum vex = dec_scan<false>(v, s_sum, &vtotal, dec_add);
         if (tile < ntiles) {
             DecTileIn ti;
             ti.state = st_in;
@@ -489,7 +453,7 @@ __global__ __launch_bounds__(kDecThreads) void wal_dec_tiles(const DecArgs A) {
         const uint64_t tile = c * kDecThreads + t;
         const uint32_t mine = tile < ntiles ? A.tsum[tile].first_code : 0u;
         uint32_t all;
-        const uint32_t ex = dec_next_nonzero(mine, s_code, &all);
+        const uint32_t ex = dec_scan<true>(mine, s_code, &all, dec_nearer);
         if (tile < ntiles) A.tin[tile].next_code = ex ? ex : next;
         if (all) next = all;
     }
@@ -534,7 +498,7 @@ __global__ __launch_bounds__(kDecThreads) void wal_dec_apply(const DecArgs A) {
             if (!cfirst && code[j] != kEvSkip && code[j] != kEvMiddle) cfirst = code[j];
         }
         DecOp total;
-        DecOp s = dec_compose(ti.state, dec_scan_op(loc, s_op, &total));
+        DecOp s = dec_compose(ti.state, dec_scan<false>(loc, s_op, &total, dec_compose));
         DecVal v[kDecPer];
         uint64_t before[kDecPer];  // the open record's bytes before the entry, kDecNone: no open record
         DecSum sum{0, 0, 0, 0};
@@ -546,9 +510,9 @@ __global__ __launch_bounds__(kDecThreads) void wal_dec_apply(const DecArgs A) {
             dec_accumulate(&sum, v[j]);
         }
         DecSum stotal;
-        const DecSum ex = dec_scan_sum(sum, s_sum, &stotal);
+        const DecSum ex = dec_scan<false>(sum, s_sum, &stotal, dec_add);
         uint32_t all;
-        uint32_t next = dec_next_nonzero(cfirst, s_code, &all);
+        uint32_t next = dec_scan<true>(cfirst, s_code, &all, dec_nearer);
         if (!next) next = ti.next_code;
         uint32_t nx[kDecPer];
 #pragma unroll
@@ -607,11 +571,9 @@ __global__ __launch_bounds__(kDecThreads) void wal_dec_apply(const DecArgs A) {
 // is one unaligned 16-B load and one aligned 16-B store; one that crosses
 // fragments is composed byte by byte and stored whole; the span's ragged ends
 // are stored byte by byte, so two workgroups never store the same byte.
-typedef uint32_t dec_u4 __attribute__((ext_vector_type(4)));
-
 __global__ __launch_bounds__(kDecThreads) void wal_unframe_kernel(const DecArgs A) {
-    __shared__ uint16_t s_out[kDecMaxFrags + 1];
-    __shared__ uint16_t s_src[kDecMaxFrags];
+    __shared__ uint16_t s_out[kWalMaxFrags + 1];
+    __shared__ uint16_t s_src[kWalMaxFrags];
     __shared__ uint32_t s_wt[kDecThreads / 64];
     __shared__ uint64_t s_span;
     if (A.head->status) return;
@@ -621,8 +583,8 @@ __global__ __launch_bounds__(kDecThreads) void wal_unframe_kernel(const DecArgs 
     for (uint64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
         const uint32_t e0 = A.bfirst[blk], e1 = A.bend[blk];
         uint32_t cnt = 0;
-        if (e0 != ~0u && e1 != ~0u && e1 > e0 && e1 <= n) cnt = e1 - e0 < kDecMaxFrags ? e1 - e0 : kDecMaxFrags;
-        const uint64_t start = blk * kDecBlock;
+        if (e0 != ~0u && e1 != ~0u && e1 > e0 && e1 <= n) cnt = e1 - e0 < kWalMaxFrags ? e1 - e0 : kWalMaxFrags;
+        const uint64_t start = blk * kWalBlock;
         __syncthreads();  // the previous block's searches are done
         uint32_t carry = 0;
         for (uint32_t k0 = 0; k0 < cnt; k0 += kDecThreads) {  // block-uniform
@@ -633,7 +595,7 @@ __global__ __launch_bounds__(kDecThreads) void wal_unframe_kernel(const DecArgs 
                 const uint64_t i = static_cast<uint64_t>(e0) + k;
                 fp = A.fpos[i];
                 if (fp != kDecNone) ll = (A.ev[i] >> 8) & 0xffffu;
-                s_src[k] = static_cast<uint16_t>(A.hdr_off[i] - start + kDecHeader);
+                s_src[k] = static_cast<uint16_t>(A.hdr_off[i] - start + kWalHeader);
             }
             const uint32_t inc = wg_incl_scan<kDecThreads / 64>(ll, s_wt);
             const uint32_t o = carry + inc - ll;
@@ -669,19 +631,11 @@ __global__ __launch_bounds__(kDecThreads) void wal_unframe_kernel(const DecArgs 
                 hi = lo + 16u < total ? lo + 16u : total;
             }
             // the fragment under lo: the last one with s_out <= lo (s_out[0] = 0)
-            uint32_t a = 0, b = cnt;
-            while (a < b) {
-                const uint32_t m = (a + b) >> 1;
-                if (s_out[m] <= lo)
-                    a = m + 1;
-                else
-                    b = m;
-            }
-            uint32_t f = a - 1;
+            uint32_t f = count_le(s_out, cnt, lo) - 1;
             if (hi - lo == 16u && lo + 16u <= s_out[f + 1]) {
-                dec_u4 v;
+                u32x4 v;
                 __builtin_memcpy(&v, src + s_src[f] + (lo - s_out[f]), 16);
-                *reinterpret_cast<dec_u4 *>(dst + lo) = v;
+                *reinterpret_cast<u32x4 *>(dst + lo) = v;
                 continue;
             }
             uint64_t wlo = 0, whi = 0;
@@ -694,17 +648,7 @@ __global__ __launch_bounds__(kDecThreads) void wal_unframe_kernel(const DecArgs 
                 else
                     whi |= byte << (8 * (q - 8));
             }
-            if (hi - lo == 16u) {
-                dec_u4 v;
-                v.x = static_cast<uint32_t>(wlo);
-                v.y = static_cast<uint32_t>(wlo >> 32);
-                v.z = static_cast<uint32_t>(whi);
-                v.w = static_cast<uint32_t>(whi >> 32);
-                *reinterpret_cast<dec_u4 *>(dst + lo) = v;
-            } else {
-                for (uint32_t q = 0; q < hi - lo; ++q)
-                    dst[lo + q] = static_cast<uint8_t>((q < 8 ? wlo >> (8 * q) : whi >> (8 * (q - 8))) & 0xffu);
-            }
+            granule_store(dst + lo, wlo, whi, (1u << (hi - lo)) - 1u);  // whole: dst + lo is 16-B aligned
         }
     }
 }
@@ -717,29 +661,31 @@ namespace {
 
 constexpr uint64_t kMaxScanCap = 0xfffffffeull;  // entry indices are 32-bit, ~0 means none
 
-struct DecWs {
-    size_t head, ev, fpos, blk, tsum, tin, total;
-    uint64_t nb, tiles;
-};
-DecWs dec_ws_layout(uint64_t cap) {
-    DecWs w;
-    w.nb = cap + 1;
-    w.tiles = (cap + lvk::kDecTile - 1) / lvk::kDecTile;
-    w.head = 0;
-    w.ev = al16(sizeof(lvk::DecHead));
-    w.fpos = w.ev + al16(cap * sizeof(uint32_t));
-    w.blk = w.fpos + al16(cap * sizeof(uint64_t));
-    w.tsum = w.blk + al16(3 * w.nb * sizeof(uint32_t));
-    w.tin = w.tsum + al16(w.tiles * sizeof(lvk::DecTileSum));
-    w.total = w.tin + al16(w.tiles * sizeof(lvk::DecTileIn));
-    return w;
+// The workspace for scan_cap = cap; returns the scan tiles.
+uint64_t dec_carve(Carve &C, uint64_t cap, lvk::DecArgs &A) {
+    const uint64_t tiles = (cap + lvk::kDecTile - 1) / lvk::kDecTile;
+    A.nb = cap + 1;
+    A.head = C.take<lvk::DecHead>(1);
+    A.ev = C.take<uint32_t>(cap);
+    A.fpos = C.take<uint64_t>(cap);
+    A.fkill = C.take<uint32_t>(3 * A.nb);  // one region, set with one memset: fkill, bfirst, bend
+    A.bfirst = A.fkill ? A.fkill + A.nb : nullptr;
+    A.bend = A.fkill ? A.bfirst + A.nb : nullptr;
+    A.tsum = C.take<lvk::DecTileSum>(tiles);
+    A.tin = C.take<lvk::DecTileIn>(tiles);
+    return tiles;
 }
 
 }  // namespace
 
 extern "C" {
 
-size_t lv_wal_decode_workspace_bytes(size_t scan_cap) { return dec_ws_layout(scan_cap).total; }
+size_t lv_wal_decode_workspace_bytes(size_t scan_cap) {
+    lvk::DecArgs A{};
+    Carve C{nullptr};
+    dec_carve(C, scan_cap, A);
+    return C.at;
+}
 
 int lv_wal_decode_device(const uint8_t *d_log, size_t bytes, const uint64_t *d_hdr_off, const uint32_t *d_crc,
                          const uint32_t *d_info, const uint64_t *d_count, size_t scan_cap,
@@ -750,7 +696,7 @@ int lv_wal_decode_device(const uint8_t *d_log, size_t bytes, const uint64_t *d_h
     const bool checksum = !(flags & LV_WAL_DECODE_NO_CHECKSUM);
     if (!out) return set_err(LV_ERR_INVALID, "null output descriptor");
     if (!out->d_totals) return set_err(LV_ERR_INVALID, "null d_totals");
-    if (reinterpret_cast<uintptr_t>(out->d_totals) % 8) return set_err(LV_ERR_INVALID, "d_totals must be 8-byte aligned");
+    if (misaligned(out->d_totals, 8)) return set_err(LV_ERR_INVALID, "d_totals must be 8-byte aligned");
     if (!d_count) return set_err(LV_ERR_INVALID, "null count pointer");
     if (!d_log && bytes) return set_err(LV_ERR_INVALID, "null log pointer");
     if (scan_cap && (!d_hdr_off || !d_info)) return set_err(LV_ERR_INVALID, "null scan array");
@@ -763,23 +709,20 @@ int lv_wal_decode_device(const uint8_t *d_log, size_t bytes, const uint64_t *d_h
         if (have != 0 && have != 3) return set_err(LV_ERR_INVALID, "null report array (all three or none)");
         if (have == 0 && out->rep_cap) return set_err(LV_ERR_INVALID, "null report array with rep_cap > 0");
     }
-    if (reinterpret_cast<uintptr_t>(d_log) % 8) return set_err(LV_ERR_INVALID, "log must be 8-byte aligned");
+    if (misaligned(d_log, 8)) return set_err(LV_ERR_INVALID, "log must be 8-byte aligned");
     if (scan_cap > kMaxScanCap) return set_err(LV_ERR_INVALID, "scan_cap too large for one decode");
     if (!d_workspace) return set_err(LV_ERR_INVALID, "null workspace");
-    if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
-    const DecWs ws = dec_ws_layout(scan_cap);
-    if (workspace_bytes < ws.total) return set_err(LV_ERR_INVALID, "workspace too small");
-    {
-        const uintptr_t o = reinterpret_cast<uintptr_t>(out->d_payload), p = reinterpret_cast<uintptr_t>(d_log);
-        if (bytes && out->payload_cap && o < p + bytes && p < o + out->payload_cap)
-            return set_err(LV_ERR_INVALID, "d_payload overlaps d_log");
-    }
+    if (misaligned(d_workspace, 16)) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
+    lvk::DecArgs A{};
+    Carve C{static_cast<uint8_t *>(d_workspace)};
+    const uint64_t tiles = dec_carve(C, scan_cap, A);
+    if (workspace_bytes < C.at) return set_err(LV_ERR_INVALID, "workspace too small");
+    if (overlaps(out->d_payload, out->payload_cap, d_log, bytes))
+        return set_err(LV_ERR_INVALID, "d_payload overlaps d_log");
     DevCtx *c = nullptr;
     if (int rc = current_ctx(&c)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *wb = static_cast<uint8_t *>(d_workspace);
 
-    lvk::DecArgs A{};
     A.log = d_log;
     A.bytes = bytes;
     A.hdr_off = d_hdr_off;
@@ -787,33 +730,24 @@ int lv_wal_decode_device(const uint8_t *d_log, size_t bytes, const uint64_t *d_h
     A.info = d_info;
     A.count = d_count;
     A.cap = scan_cap;
-    A.nb = ws.nb;
     A.nblocks = (static_cast<uint64_t>(bytes) + LV_WAL_BLOCK_SIZE - 1) / LV_WAL_BLOCK_SIZE;
     A.out = *out;
     if (!A.out.d_rep_bytes) A.out.rep_cap = 0;
-    A.head = reinterpret_cast<lvk::DecHead *>(wb + ws.head);
-    A.ev = reinterpret_cast<uint32_t *>(wb + ws.ev);
-    A.fpos = reinterpret_cast<uint64_t *>(wb + ws.fpos);
-    A.fkill = reinterpret_cast<uint32_t *>(wb + ws.blk);
-    A.bfirst = A.fkill + ws.nb;
-    A.bend = A.bfirst + ws.nb;
-    A.tsum = reinterpret_cast<lvk::DecTileSum *>(wb + ws.tsum);
-    A.tin = reinterpret_cast<lvk::DecTileIn *>(wb + ws.tin);
 
     const uint64_t cus = static_cast<uint64_t>(c->cus > 0 ? c->cus : 1);
     const dim3 b(lvk::kDecThreads);
     if (scan_cap) {
-        LV_HIP(hipMemsetAsync(A.fkill, 0xff, 3 * ws.nb * sizeof(uint32_t), s));
+        LV_HIP(hipMemsetAsync(A.fkill, 0xff, 3 * A.nb * sizeof(uint32_t), s));
         const uint64_t g1 = std::min<uint64_t>((scan_cap + lvk::kDecThreads - 1) / lvk::kDecThreads, 16 * cus);
         hipLaunchKernelGGL(lvk::wal_dec_classify, dim3(static_cast<uint32_t>(g1)), b, 0, s, A);
-        const uint64_t g2 = std::min<uint64_t>(ws.tiles, 8 * cus);
+        const uint64_t g2 = std::min<uint64_t>(tiles, 8 * cus);
         hipLaunchKernelGGL(lvk::wal_dec_reduce, dim3(static_cast<uint32_t>(g2)), b, 0, s, A);
     }
     hipLaunchKernelGGL(lvk::wal_dec_tiles, dim3(1), b, 0, s, A);
     if (scan_cap) {
-        const uint64_t g4 = std::min<uint64_t>(ws.tiles, 8 * cus);
+        const uint64_t g4 = std::min<uint64_t>(tiles, 8 * cus);
         hipLaunchKernelGGL(lvk::wal_dec_apply, dim3(static_cast<uint32_t>(g4)), b, 0, s, A);
-        const uint64_t g5 = std::min<uint64_t>(std::min<uint64_t>(A.nblocks, ws.nb), 8 * cus);
+        const uint64_t g5 = std::min<uint64_t>(std::min<uint64_t>(A.nblocks, A.nb), 8 * cus);
         if (g5) hipLaunchKernelGGL(lvk::wal_unframe_kernel, dim3(static_cast<uint32_t>(g5)), b, 0, s, A);
     }
     g_kernel = "wal_dec_classify+wal_dec_reduce+wal_dec_tiles+wal_dec_apply+wal_unframe_kernel";

@@ -14,6 +14,7 @@
 #include "../../include/lvgpu/wal.h"
 #include "lv_internal.h"
 #include "lvh.h"
+#include "lvk/wal.h"
 
 namespace lvk {
 
@@ -32,10 +33,7 @@ namespace lvk {
 // bytes are output bytes, else byte by byte.  Work per lane follows the
 // output bytes: 20,000 one-byte records and one 4 MiB record balance alike.
 constexpr uint32_t kFrameThreads = 256;
-constexpr uint32_t kFrameBlock = 32768;                   // log_format.rs:63
-constexpr uint32_t kFrameHeader = 7;                      // log_format.rs:66
-constexpr uint32_t kFrameMaxFrags = kFrameBlock / kFrameHeader + 1;  // headers that fit one block
-constexpr uint64_t kFramePosMask = (1ull << 56) - 1;      // pos words: out_pos | type << 56
+constexpr uint64_t kFramePosMask = (1ull << 56) - 1;  // pos words: out_pos | type << 56
 
 struct FrameArgs {
     const uint8_t *payload;
@@ -51,8 +49,6 @@ struct FrameArgs {
     const uint32_t *crc;   // masked CRC of each fragment (the CRC step's output)
     const uint32_t *bidx;  // first fragment of each block, nblocks + 1 entries
 };
-
-typedef uint32_t frame_u4 __attribute__((ext_vector_type(4)));
 
 // One fragment's header fields and the position of the next header.
 struct FrameFrag {
@@ -94,8 +90,8 @@ __device__ __forceinline__ void frame_compose(const FrameArgs &A, int64_t p0, in
                 b = (r.len >> (8 * (d - 4))) & 0xffu;
             else if (d == 6)
                 b = r.type;
-            else if (d < kFrameHeader + r.len)
-                b = A.payload[r.src + d - kFrameHeader];
+            else if (d < kWalHeader + r.len)
+                b = A.payload[r.src + d - kWalHeader];
             // else: the block's zero trailer
         }
         if (k < 8)
@@ -103,31 +99,20 @@ __device__ __forceinline__ void frame_compose(const FrameArgs &A, int64_t p0, in
         else
             hi |= static_cast<uint64_t>(b) << (8 * (k - 8));
     }
-    uint8_t *q = A.out + p0;  // 16-B aligned by construction (only dereferenced at valid bytes)
-    if (valid == 0xffffu) {
-        frame_u4 v;
-        v.x = static_cast<uint32_t>(lo);
-        v.y = static_cast<uint32_t>(lo >> 32);
-        v.z = static_cast<uint32_t>(hi);
-        v.w = static_cast<uint32_t>(hi >> 32);
-        *reinterpret_cast<frame_u4 *>(q) = v;
-    } else {
-        for (uint32_t k = 0; k < 16; ++k)
-            if (valid & (1u << k)) q[k] = static_cast<uint8_t>((k < 8 ? lo >> (8 * k) : hi >> (8 * (k - 8))) & 0xffu);
-    }
+    granule_store(A.out + p0, lo, hi, valid);  // 16-B aligned by construction (only dereferenced at valid bytes)
 }
 
 __global__ __launch_bounds__(kFrameThreads) void wal_frame_kernel(const FrameArgs A) {
-    __shared__ uint16_t s_pos[kFrameMaxFrags];
+    __shared__ uint16_t s_pos[kWalMaxFrags];
     const uint32_t tid = threadIdx.x;
     for (uint64_t blk = blockIdx.x; blk < A.nblocks; blk += gridDim.x) {
         // output positions of this block: [lo, hi)
-        const uint64_t lo = blk == 0 ? 0 : blk * kFrameBlock - A.first;
-        const uint64_t end = (blk + 1) * kFrameBlock - A.first;
+        const uint64_t lo = blk == 0 ? 0 : blk * kWalBlock - A.first;
+        const uint64_t end = (blk + 1) * kWalBlock - A.first;
         const uint64_t hi = end < A.out_len ? end : A.out_len;
         const uint32_t f0 = A.bidx[blk];
         const uint32_t cnt = A.bidx[blk + 1] - f0;
-        const uint32_t nf = cnt < kFrameMaxFrags ? cnt : kFrameMaxFrags;
+        const uint32_t nf = cnt < kWalMaxFrags ? cnt : kWalMaxFrags;
         __syncthreads();  // the previous block's searches are done
         for (uint32_t i = tid; i < nf; i += kFrameThreads)
             s_pos[i] = static_cast<uint16_t>((A.pos[f0 + i] & kFramePosMask) - lo);
@@ -138,23 +123,16 @@ __global__ __launch_bounds__(kFrameThreads) void wal_frame_kernel(const FrameArg
         for (uint64_t g = g_lo + tid; g < g_hi; g += kFrameThreads) {
             const int64_t p0 = static_cast<int64_t>(g * 16) - static_cast<int64_t>(A.align);
             const uint32_t rel = static_cast<uint32_t>((p0 < 0 ? 0 : p0) - static_cast<int64_t>(lo));
-            // last fragment of the block with s_pos <= rel (idx = count of such)
-            uint32_t a = 0, b = nf;
-            while (a < b) {
-                const uint32_t m = (a + b) >> 1;
-                if (s_pos[m] <= rel)
-                    a = m + 1;
-                else
-                    b = m;
-            }
+            // the last fragment of the block with s_pos <= rel is the one before a
+            const uint32_t a = count_le(s_pos, nf, rel);
             const int64_t f = static_cast<int64_t>(f0) + a - 1;  // (block 0 before its first header: f0 - 1 = -1)
             if (a > 0 && p0 >= 0) {
                 const uint32_t d = rel - s_pos[a - 1];
                 const uint32_t len = A.len[f];
-                if (d >= kFrameHeader && d + 16 <= kFrameHeader + len) {
-                    frame_u4 v;
-                    __builtin_memcpy(&v, A.payload + A.src[f] + (d - kFrameHeader), 16);
-                    *reinterpret_cast<frame_u4 *>(A.out + p0) = v;
+                if (d >= kWalHeader && d + 16 <= kWalHeader + len) {
+                    u32x4 v;
+                    __builtin_memcpy(&v, A.payload + A.src[f] + (d - kWalHeader), 16);
+                    *reinterpret_cast<u32x4 *>(A.out + p0) = v;
                     continue;
                 }
             }
@@ -173,23 +151,26 @@ constexpr uint64_t kMaxFragments = 0xffffffffull;  // one lv_crc32c_batch_device
 
 // Workspace: the fragment table (the upload image, one copy), the CRCs, then
 // the offsets API's sort workspace.
-struct EncWs {
-    size_t src, pos, len, seed, bidx, crc, image, sort, total;
+// It is carved three times: without a buffer to measure, over the caller's
+// workspace, and over the pinned staging slot the table is written in (only
+// the first `image` bytes of that one exist).
+struct EncTab {
+    uint64_t *src, *pos;
+    uint32_t *len, *seed, *bidx, *crc;
+    size_t image;   // bytes the upload covers
+    uint8_t *sort;  // the rest, for lv_crc32c_batch_device_hint
 };
-EncWs enc_ws_layout(uint64_t fragments) {
-    EncWs w;
-    w.src = 0;
-    w.pos = w.src + al16(fragments * sizeof(uint64_t));
-    w.len = w.pos + al16(fragments * sizeof(uint64_t));
-    w.seed = w.len + al16(fragments * sizeof(uint32_t));
+void enc_carve(Carve &C, uint64_t fragments, EncTab &T) {
+    T.src = C.take<uint64_t>(fragments);
+    T.pos = C.take<uint64_t>(fragments);
+    T.len = C.take<uint32_t>(fragments);
+    T.seed = C.take<uint32_t>(fragments);
     // every block of the span but the first starts with a header: at most
     // fragments + 1 blocks, plus the closing entry
-    w.bidx = w.seed + al16(fragments * sizeof(uint32_t));
-    w.crc = w.bidx + al16((fragments + 2) * sizeof(uint32_t));
-    w.image = w.crc + al16(fragments * sizeof(uint32_t));  // bytes the upload covers
-    w.sort = w.image;
-    w.total = w.sort + al16(lv_crc32c_workspace_bytes(fragments));
-    return w;
+    T.bidx = C.take<uint32_t>(fragments + 2);
+    T.crc = C.take<uint32_t>(fragments);
+    T.image = C.at;
+    T.sort = C.take<uint8_t>(lv_crc32c_workspace_bytes(fragments));
 }
 
 // Page-locked staging for the table upload.  A slot is busy until the event
@@ -232,7 +213,12 @@ int stage_acquire(int dev, size_t need, size_t *slot) {
 
 extern "C" {
 
-size_t lv_wal_encode_workspace_bytes(size_t fragments) { return enc_ws_layout(fragments).total; }
+size_t lv_wal_encode_workspace_bytes(size_t fragments) {
+    EncTab T;
+    Carve C{nullptr};
+    enc_carve(C, fragments, T);
+    return C.at;
+}
 
 int lv_wal_encode_device(const uint8_t *d_payload, uint64_t payload_bytes, const uint64_t *rec_off,
                          const uint64_t *rec_len, size_t n, uint64_t dest_length, uint8_t *d_out, size_t out_cap,
@@ -260,49 +246,47 @@ int lv_wal_encode_device(const uint8_t *d_payload, uint64_t payload_bytes, const
     if (out_cap < lay.out_len || (!d_out && lay.out_len)) return set_err(LV_ERR_INVALID, "output buffer too small");
     if (lay.out_len == 0) return LV_OK;  // no records: nothing to enqueue
     if (!d_workspace) return set_err(LV_ERR_INVALID, "null workspace");
-    if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
+    if (misaligned(d_workspace, 16)) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
     const uint64_t F = lay.fragments;
-    const EncWs ws = enc_ws_layout(F);
-    if (workspace_bytes < ws.total) return set_err(LV_ERR_INVALID, "workspace too small");
-    {
-        const uintptr_t o = reinterpret_cast<uintptr_t>(d_out), p = reinterpret_cast<uintptr_t>(d_payload);
-        if (payload_bytes && o < p + payload_bytes && p < o + lay.out_len)
-            return set_err(LV_ERR_INVALID, "d_out overlaps d_payload");
-    }
+    EncTab D;  // the table on the device
+    Carve C{static_cast<uint8_t *>(d_workspace)};
+    enc_carve(C, F, D);
+    if (workspace_bytes < C.at) return set_err(LV_ERR_INVALID, "workspace too small");
+    if (overlaps(d_out, lay.out_len, d_payload, payload_bytes))
+        return set_err(LV_ERR_INVALID, "d_out overlaps d_payload");
     if (count_first) lvgpu_internal::wal_layout(rec_off, rec_len, n, dest_length, true, &lay);
     DevCtx *c = nullptr;
     if (int rc = current_ctx(&c)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *wb = static_cast<uint8_t *>(d_workspace);
 
     // Step a: the fragment table, through staging the library owns.
-    uint32_t type_crc[5];
-    for (uint8_t t = 0; t < 5; ++t) type_crc[t] = lv_crc32c_value(&t, 1);  // log_writer.rs:136-142
+    uint32_t type_crc[5], type_masked[5];
+    for (uint8_t t = 0; t < 5; ++t) {
+        type_crc[t] = lv_crc32c_value(&t, 1);  // log_writer.rs:136-142
+        type_masked[t] = lv_crc32c_mask(type_crc[t]);
+    }
     uint64_t total = 0;
     uint32_t max_len = 0;
     {
         std::lock_guard<std::mutex> lk(g_stage_m);
         size_t slot = 0;
-        if (int rc = stage_acquire(c->dev, ws.image, &slot)) return rc;
+        if (int rc = stage_acquire(c->dev, D.image, &slot)) return rc;
         StageSlot &st = (*g_stage)[slot];
-        uint64_t *h_src = reinterpret_cast<uint64_t *>(st.p + ws.src);
-        uint64_t *h_pos = reinterpret_cast<uint64_t *>(st.p + ws.pos);
-        uint32_t *h_len = reinterpret_cast<uint32_t *>(st.p + ws.len);
-        uint32_t *h_seed = reinterpret_cast<uint32_t *>(st.p + ws.seed);
-        uint32_t *h_bidx = reinterpret_cast<uint32_t *>(st.p + ws.bidx);
-        uint32_t *h_crc = reinterpret_cast<uint32_t *>(st.p + ws.crc);
+        EncTab H;  // its image in the slot
+        Carve S{st.p};
+        enc_carve(S, F, H);
         for (uint64_t i = 0; i < F; ++i) {
             const lvgpu_internal::WalFrag &f = lay.frags[i];
-            h_src[i] = f.src;
-            h_pos[i] = f.out_pos | (static_cast<uint64_t>(f.type) << 56);
-            h_len[i] = f.len;
-            h_seed[i] = type_crc[f.type];
-            h_crc[i] = lv_crc32c_mask(type_crc[f.type]);  // the CRC of an empty fragment (step a overwrites it)
+            H.src[i] = f.src;
+            H.pos[i] = f.out_pos | (static_cast<uint64_t>(f.type) << 56);
+            H.len[i] = f.len;
+            H.seed[i] = type_crc[f.type];
+            H.crc[i] = type_masked[f.type];  // the CRC of an empty fragment (step a overwrites it)
             total += f.len;
             max_len = std::max(max_len, f.len);
         }
-        for (size_t k = 0; k < lay.block_first.size(); ++k) h_bidx[k] = static_cast<uint32_t>(lay.block_first[k]);
-        LV_HIP(hipMemcpyAsync(wb, st.p, ws.image, hipMemcpyHostToDevice, s));
+        for (size_t k = 0; k < lay.block_first.size(); ++k) H.bidx[k] = static_cast<uint32_t>(lay.block_first[k]);
+        LV_HIP(hipMemcpyAsync(d_workspace, st.p, D.image, hipMemcpyHostToDevice, s));
         const hipError_t e = hipEventRecord(st.done, s);
         if (e != hipSuccess) {
             st.retired = true;  // the copy may still be reading the slot and nothing tells when it ends
@@ -310,16 +294,12 @@ int lv_wal_encode_device(const uint8_t *d_payload, uint64_t payload_bytes, const
         }
         st.used = true;
     }
-    uint32_t *d_crc = reinterpret_cast<uint32_t *>(wb + ws.crc);
-    const uint64_t *d_src = reinterpret_cast<const uint64_t *>(wb + ws.src);
-    const uint32_t *d_len = reinterpret_cast<const uint32_t *>(wb + ws.len);
-    const uint32_t *d_seed = reinterpret_cast<const uint32_t *>(wb + ws.seed);
     // A batch with no payload bytes (every record empty) has nothing to
     // checksum, and possibly no payload buffer: the uploaded CRCs stand.
     const lv_batch_hint hint{total, max_len, 0};
     if (total)
-        if (int rc = lv_crc32c_batch_device_hint(d_payload, d_src, d_len, d_seed, d_crc, F, LV_CRC_MASK, &hint,
-                                                 wb + ws.sort, workspace_bytes - ws.sort, stream))
+        if (int rc = lv_crc32c_batch_device_hint(d_payload, D.src, D.len, D.seed, D.crc, F, LV_CRC_MASK, &hint, D.sort,
+                                                 workspace_bytes - D.image, stream))
             return rc;
 
     // Step b: the log bytes.
@@ -331,11 +311,11 @@ int lv_wal_encode_device(const uint8_t *d_payload, uint64_t payload_bytes, const
     A.align = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(d_out) % 16);
     A.nblocks = lay.block_first.size() - 1;
     A.nfrags = F;
-    A.src = d_src;
-    A.pos = reinterpret_cast<const uint64_t *>(wb + ws.pos);
-    A.len = d_len;
-    A.crc = d_crc;
-    A.bidx = reinterpret_cast<const uint32_t *>(wb + ws.bidx);
+    A.src = D.src;
+    A.pos = D.pos;
+    A.len = D.len;
+    A.crc = D.crc;
+    A.bidx = D.bidx;
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(A.nblocks, 8ull * static_cast<uint64_t>(c->cus)));
     hipLaunchKernelGGL(lvk::wal_frame_kernel, dim3(grid), dim3(lvk::kFrameThreads), 0, s, A);
     return check_launch();

@@ -16,6 +16,7 @@
 #include "lv_internal.h"
 #include "lvh.h"
 #include "lvk/sort.h"
+#include "lvk/wal.h"
 
 namespace lvk {
 
@@ -36,9 +37,7 @@ namespace lvk {
 // units (by sorted position; wal_unsort writes them in log order).  Five
 // launches, no host synchronisation (round 1: count pass, hipCUB
 // scan, host readback of the total, emit pass, then the whole offsets API).
-constexpr uint32_t kWalBlock = 32768;  // log_format.rs:63
-constexpr uint32_t kWalHeader = 7;     // log_format.rs:66
-constexpr uint32_t kHdrCache = 64;     // headers per block wal_hist keeps for wal_scatter
+constexpr uint32_t kHdrCache = 64;  // headers per block wal_hist keeps for wal_scatter
 
 // A cached header: position in its block | length << 16 | type << 32.
 __device__ __forceinline__ uint64_t hdr_pack(uint32_t pos, uint32_t len, uint32_t type) {
@@ -382,28 +381,44 @@ static uint64_t wal_wgs(uint64_t nblocks, uint64_t *chunk) {
     return wgs;
 }
 
+// The workspace of a scan of `bytes` of log at capacity `cap`, and how the
+// blocks are shared out.  It starts as the sort workspace does (lvk/sort.h:
+// the header, the histogram matrix, the workgroups' sums), so sort_scan and the
+// class kernel read it as one.
 struct WalWs {
-    size_t m, wgrec, blk, hc, ent, tmp, pos, total;
+    uint64_t nblocks, wgs, chunk;
+    uint32_t *ws, *M;
+    uint64_t *wgrec;
+    uint32_t *blk;     // records of each block
+    uint64_t *hc;      // each block's first kHdrCache headers
+    uint4 *ent;        // the sorted entries
+    uint32_t *tmp, *spos;  // with LVK_WAL_UNSORT: the CRCs by sorted position, each record's sorted position
 };
+// (The header, a block's cached headers and an entry are whole 16-B units:
+// no region of these is padded.)
+static_assert(lvk::kWsHeader * sizeof(uint32_t) % 16 == 0 && lvk::kHdrCache * sizeof(uint64_t) % 16 == 0 &&
+                  sizeof(uint4) == 16,
+              "the scan workspace's unpadded regions");
 
-static WalWs wal_ws_layout(uint64_t bytes, uint64_t cap) {
-    const uint64_t nblocks = (bytes + lvk::kWalBlock - 1) / lvk::kWalBlock;
-    uint64_t chunk = 0;
-    const uint64_t wgs = wal_wgs(nblocks, &chunk);
-    WalWs w;
-    w.m = lvk::kWsHeader * sizeof(uint32_t);
-    w.wgrec = w.m + al16(wgs * lvk::kKeys * sizeof(uint32_t));
-    w.blk = w.wgrec + al16(wgs * sizeof(uint64_t));
-    w.hc = w.blk + al16(nblocks * sizeof(uint32_t));
-    w.ent = w.hc + nblocks * lvk::kHdrCache * sizeof(uint64_t);
-    // with LVK_WAL_UNSORT: the CRCs by sorted position and each record's sorted position
-    w.tmp = w.ent + cap * sizeof(uint4);
-    w.pos = w.tmp + (LVK_WAL_UNSORT ? al16(cap * sizeof(uint32_t)) : 0);
-    w.total = w.pos + (LVK_WAL_UNSORT ? al16(cap * sizeof(uint32_t)) : 0);
-    return w;
+static void wal_carve(Carve &C, uint64_t bytes, uint64_t cap, WalWs &W) {
+    W.nblocks = (bytes + lvk::kWalBlock - 1) / lvk::kWalBlock;
+    W.wgs = wal_wgs(W.nblocks, &W.chunk);
+    W.ws = C.take<uint32_t>(lvk::kWsHeader);
+    W.M = C.take<uint32_t>(W.wgs * lvk::kKeys);
+    W.wgrec = C.take<uint64_t>(W.wgs);
+    W.blk = C.take<uint32_t>(W.nblocks);
+    W.hc = C.take<uint64_t>(W.nblocks * lvk::kHdrCache);
+    W.ent = C.take<uint4>(cap);
+    W.tmp = LVK_WAL_UNSORT ? C.take<uint32_t>(cap) : nullptr;
+    W.spos = LVK_WAL_UNSORT ? C.take<uint32_t>(cap) : nullptr;
 }
 
-size_t lv_wal_scan_workspace_bytes(size_t bytes, size_t cap) { return wal_ws_layout(bytes, cap).total; }
+size_t lv_wal_scan_workspace_bytes(size_t bytes, size_t cap) {
+    WalWs W;
+    Carve C{nullptr};
+    wal_carve(C, bytes, cap, W);
+    return C.at;
+}
 
 int lv_wal_scan_device(const uint8_t *d_log, size_t bytes, uint64_t *d_hdr_off, uint32_t *d_crc, uint32_t *d_info,
                        size_t cap, uint64_t *d_count, void *d_workspace, size_t workspace_bytes, void *stream) {
@@ -411,58 +426,48 @@ int lv_wal_scan_device(const uint8_t *d_log, size_t bytes, uint64_t *d_hdr_off, 
     if (!d_count) return set_err(LV_ERR_INVALID, "null count pointer");
     if ((!d_log && bytes) || (cap && (!d_hdr_off || !d_crc || !d_info)) || !d_workspace)
         return set_err(LV_ERR_INVALID, "null device pointer");
-    if (reinterpret_cast<uintptr_t>(d_log) % 8) return set_err(LV_ERR_INVALID, "log must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
+    if (misaligned(d_log, 8)) return set_err(LV_ERR_INVALID, "log must be 8-byte aligned");
+    if (misaligned(d_workspace, 16)) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
     if (bytes / lvk::kWalHeader >= 0xffffffffull || cap > 0xffffffffull)
         return set_err(LV_ERR_INVALID, "log too large for one scan");
-    const WalWs lay = wal_ws_layout(bytes, cap);
-    if (workspace_bytes < lv_wal_scan_workspace_bytes(bytes, cap)) return set_err(LV_ERR_INVALID, "workspace too small");
+    WalWs W;
+    Carve C{static_cast<uint8_t *>(d_workspace)};
+    wal_carve(C, bytes, cap, W);
+    if (workspace_bytes < C.at) return set_err(LV_ERR_INVALID, "workspace too small");
     DevCtx *c = nullptr;
     if (int rc = current_ctx(&c)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint64_t nblocks = (bytes + lvk::kWalBlock - 1) / lvk::kWalBlock;
-    if (nblocks == 0) {
+    if (W.nblocks == 0) {
         LV_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), s));
         return LV_OK;
     }
-    uint8_t *wb = static_cast<uint8_t *>(d_workspace);
     // (Round 5 measured a one-launch scan beside this one -- every workgroup
     // framing, sorting and checksumming its own blocks -- at 0.622 of 8 TB/s
     // against 0.632: its per-workgroup rounds ended ragged and the slowest
     // workgroup set the launch, profiles/r05/wal_paths/.  Round 6 removed it.)
-    uint32_t *ws = reinterpret_cast<uint32_t *>(wb);
-    uint32_t *M = reinterpret_cast<uint32_t *>(wb + lay.m);
-    uint64_t *wgrec = reinterpret_cast<uint64_t *>(wb + lay.wgrec);
-    uint32_t *blk = reinterpret_cast<uint32_t *>(wb + lay.blk);
-    uint64_t *hc = reinterpret_cast<uint64_t *>(wb + lay.hc);
-    uint4 *ent = reinterpret_cast<uint4 *>(wb + lay.ent);
-    uint64_t chunk = 0;
-    const uint64_t wgs = wal_wgs(nblocks, &chunk);
-    const dim3 g(static_cast<uint32_t>(wgs)), b(lvk::kSortThreads);
-    hipLaunchKernelGGL(lvk::wal_hist, g, dim3(lvk::kWalHistThreads), 0, s, d_log, static_cast<uint64_t>(bytes), nblocks,
-                       chunk, M, wgrec, blk, hc);
+    const dim3 g(static_cast<uint32_t>(W.wgs)), b(lvk::kSortThreads);
+    hipLaunchKernelGGL(lvk::wal_hist, g, dim3(lvk::kWalHistThreads), 0, s, d_log, static_cast<uint64_t>(bytes),
+                       W.nblocks, W.chunk, W.M, W.wgrec, W.blk, W.hc);
     // (Round 3: claiming each workgroup's key runs with device atomics in
     // wal_hist instead of this column scan -- a memset of the totals first --
     // measured 0.6 % slower: the memset launch and wal_hist's returning
     // atomics cost more than sort_scan, profiles/r03/wal2/atomic_totals/.)
-    launch_sort_scan(M, static_cast<uint32_t>(wgs), ws, wgrec, s);
-    uint32_t *tmp = LVK_WAL_UNSORT ? reinterpret_cast<uint32_t *>(wb + lay.tmp) : nullptr;
-    uint32_t *spos = LVK_WAL_UNSORT ? reinterpret_cast<uint32_t *>(wb + lay.pos) : nullptr;
-    lvk::WalOut o{d_hdr_off, d_info, d_count, cap, spos};
-    hipLaunchKernelGGL(lvk::wal_scatter, g, b, 0, s, d_log, static_cast<uint64_t>(bytes), nblocks, chunk, ws, M, wgrec,
-                       blk, hc, ent, o);
+    launch_sort_scan(W.M, static_cast<uint32_t>(W.wgs), W.ws, W.wgrec, s);
+    lvk::WalOut o{d_hdr_off, d_info, d_count, cap, W.spos};
+    hipLaunchKernelGGL(lvk::wal_scatter, g, b, 0, s, d_log, static_cast<uint64_t>(bytes), W.nblocks, W.chunk, W.ws, W.M,
+                       W.wgrec, W.blk, W.hc, W.ent, o);
     lvk::Params P{};
     P.base = reinterpret_cast<uint64_t>(d_log);
     P.out = d_crc;
     P.n = cap;
     P.nplain = cap;
-    P.ent = ent;
-    P.tmp = tmp;
-    launch_classes(*c, false, P, ws, s);
+    P.ent = W.ent;
+    P.tmp = W.tmp;
+    launch_classes(*c, false, P, W.ws, s);
     g_kernel = "wal_hist+sort_scan+wal_scatter+crc32c_classes_kernel";
-    if (tmp && cap) {
+    if (W.tmp && cap) {
         hipLaunchKernelGGL(lvk::wal_unsort, dim3(static_cast<uint32_t>(std::min<uint64_t>(c->cus, (cap + 1023) / 1024))),
-                           dim3(1024), 0, s, ws, tmp, spos, d_crc, static_cast<uint64_t>(cap));
+                           dim3(1024), 0, s, W.ws, W.tmp, W.spos, d_crc, static_cast<uint64_t>(cap));
         g_kernel = "wal_hist+sort_scan+wal_scatter+crc32c_classes_kernel+wal_unsort";
     }
     return check_launch();
@@ -471,8 +476,6 @@ int lv_wal_scan_device(const uint8_t *d_log, size_t bytes, uint64_t *d_hdr_off, 
 }  // extern "C"
 
 namespace {
-
-constexpr size_t align16(size_t x) { return (x + 15) & ~static_cast<size_t>(15); }
 
 int hip_err(hipError_t e, const char *what) {
     if (e == hipSuccess) return LV_OK;
@@ -496,13 +499,13 @@ int lvgpu_internal::scan_host_range(const uint8_t *log, size_t bytes, uint64_t b
     uint64_t cap = std::max<uint64_t>(bytes / 256, nblocks * 8), count = 0;
     int rc = LV_OK;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        const size_t wsb = align16(lv_wal_scan_workspace_bytes(bytes, cap));
-        const size_t need = wsb + align16(cap * 8) + 2 * align16(cap * 4) + 16;
+        const size_t wsb = al16(lv_wal_scan_workspace_bytes(bytes, cap));
+        const size_t need = wsb + al16(cap * 8) + 2 * al16(cap * 4) + 16;
         uint8_t *scr = nullptr;
         if ((rc = lvgpu_internal::host_scratch(&hp, 0, need, &scr))) break;
         uint64_t *d_hdr = reinterpret_cast<uint64_t *>(scr + wsb);
-        uint32_t *d_crc = reinterpret_cast<uint32_t *>(scr + wsb + align16(cap * 8));
-        uint32_t *d_info = reinterpret_cast<uint32_t *>(scr + wsb + align16(cap * 8) + align16(cap * 4));
+        uint32_t *d_crc = reinterpret_cast<uint32_t *>(scr + wsb + al16(cap * 8));
+        uint32_t *d_info = reinterpret_cast<uint32_t *>(scr + wsb + al16(cap * 8) + al16(cap * 4));
         uint64_t *d_count = reinterpret_cast<uint64_t *>(scr + need - 16);
         if ((rc = lv_wal_scan_device(hp.d_arena, bytes, d_hdr, d_crc, d_info, cap, d_count, scr, wsb, s))) break;
         if ((rc = hip_err(hipMemcpyAsync(&count, d_count, 8, hipMemcpyDeviceToHost, s), "D2H")) ||
@@ -587,13 +590,13 @@ struct PipeSlot {
 // The slot's chunk (already on the device) scanned at capacity sl.cap, the
 // count copied back to the pinned word.
 int pipe_scan(PipeSlot &sl) {
-    const size_t wsb = align16(lv_wal_scan_workspace_bytes(sl.len, sl.cap));
-    const size_t need = wsb + align16(sl.cap * 8) + 2 * align16(sl.cap * 4) + 16;
+    const size_t wsb = al16(lv_wal_scan_workspace_bytes(sl.len, sl.cap));
+    const size_t need = wsb + al16(sl.cap * 8) + 2 * al16(sl.cap * 4) + 16;
     if (int rc = grow_dev(sl.scr, sl.scr_cap, need)) return rc;
     uint8_t *scr = *sl.scr;
     sl.d_hdr = reinterpret_cast<uint64_t *>(scr + wsb);
-    sl.d_crc = reinterpret_cast<uint32_t *>(scr + wsb + align16(sl.cap * 8));
-    sl.d_info = reinterpret_cast<uint32_t *>(scr + wsb + align16(sl.cap * 8) + align16(sl.cap * 4));
+    sl.d_crc = reinterpret_cast<uint32_t *>(scr + wsb + al16(sl.cap * 8));
+    sl.d_info = reinterpret_cast<uint32_t *>(scr + wsb + al16(sl.cap * 8) + al16(sl.cap * 4));
     sl.d_count = reinterpret_cast<uint64_t *>(scr + need - 16);
     if (int rc = lv_wal_scan_device(*sl.d_log, sl.len, sl.d_hdr, sl.d_crc, sl.d_info, sl.cap, sl.d_count, scr, wsb,
                                     sl.s))

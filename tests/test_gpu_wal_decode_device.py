@@ -8,7 +8,7 @@ import pytest
 
 import wal_oracle as W
 from wal_decode_cases import (B, BIG, CANARY, H, carry_log, check, collect, first_of_type, flip, guards_ok, headers,
-                              mixed_log, oracle_read, reason_cases, run_decode, shape_cases, untouched)
+                              mixed_log, oracle_read, reason_cases, run_decode, set_type, shape_cases, untouched)
 from wal_encode_cases import oracle_encode, pack, random_records, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -121,6 +121,27 @@ def test_carry_with_mismatch_in_middle(gpu):
         flip(log, first_of_type(log, W.MIDDLE) + H + 9)
         _, want = check(torch, gpu, log, tag=p)
         assert [r for _, r in want[2]][:2] == ["checksum mismatch", "error in middle of record"]
+
+
+def test_second_round_of_tile_scan(gpu):
+    """More scan tiles than one workgroup has threads: wal_dec_tiles goes round
+    twice.  256 tiles of one-byte records, then 1,025 more; a FIRST / MIDDLE /
+    LAST triple of them lies astride the round boundary (its FIRST is the last
+    entry of the first round, so the open record is carried into the second and
+    the FIRST learns of its LAST from there), and a checksum mismatch follows
+    in the second round."""
+    import torch
+    import lvgpu.wal as LW
+    R = 256 * LW.DECODE_TILE  # entries of one round
+    assert R == 262144
+    log = bytearray(oracle_encode([b"a"]) * (R + 1025))  # entry i is the 8 bytes at 8 i
+    for i, t in ((R - 1, W.FIRST), (R, W.MIDDLE), (R + 1, W.LAST)):
+        set_type(log, 8 * i, t)
+    flip(log, 8 * (R + 500) + H)
+    r, want = check(torch, gpu, log)
+    assert r.count == R + 1025
+    assert len(want[0]) == R + 500 - 2 and want[0][R - 1] == b"aaa" and want[1][R - 1] == 8 * (R - 1)
+    assert [x for _, x in want[2]] == ["checksum mismatch"]
 
 
 def test_more_blocks_than_compute_units(gpu):

@@ -1,4 +1,4 @@
-"""The workspace sizes of the four pipeline stages that take one, pinned.
+"""The workspace sizes of the pipeline stages that take one, pinned.
 
 A caller sizes its buffer with lv_*_workspace_bytes and the device entry point
 cuts the same buffer into regions, so the numbers are part of what a caller
@@ -8,11 +8,19 @@ workspace came to be described once (one function that carves the regions,
 run without a buffer to measure): that commit was built and these functions
 called on it; they need no GPU.  Capacities lie either side of each stage's
 tile (256 records, 512 and 1,024 entries, 1,024 blocks), and one lies beyond
-each documented limit."""
+each documented limit.
+
+The three WAL stages (scan, decode, encode) came to it later, the same way:
+their literals are from a build of the commit before their workspaces were
+carved.  The scan's log sizes lie either side of one 32 KiB block and of one
+workgroup's 64 blocks; decode and encode go on to the largest capacity one
+call takes (entry and fragment indices are 32-bit) and, for decode, one past
+it."""
 import pytest
 
 import lvgpu.memtable as MT
 import lvgpu.table as T
+import lvgpu.wal as LW
 import lvgpu.write_batch as WB
 
 CAPS = (0, 1, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 100000)
@@ -51,6 +59,19 @@ SST_SCAN = (
     (112, 16624, 57568, 57616),
     (112, 1601776, 1642688, 1642768),
 )
+WAL_LOG_BYTES = (0, 1, 32768, 32769, 64 * 32768, 64 * 32768 + 1)
+# rows: log bytes in WAL_LOG_BYTES; columns: cap in CAPS
+WAL_SCAN = (
+    (3152, 3200, 9280, 9296, 9344, 15424, 15440, 15488, 27712, 27728, 27776, 2403152),
+    (3680, 3728, 9808, 9824, 9872, 15952, 15968, 16016, 28240, 28256, 28304, 2403680),
+    (3680, 3728, 9808, 9824, 9872, 15952, 15968, 16016, 28240, 28256, 28304, 2403680),
+    (4192, 4240, 10320, 10336, 10384, 16464, 16480, 16528, 28752, 28768, 28816, 2404192),
+    (36176, 36224, 42304, 42320, 42368, 48448, 48464, 48512, 60736, 60752, 60800, 2436176),
+    (37728, 37776, 43856, 43872, 43920, 50000, 50016, 50064, 62288, 62304, 62352, 2437728),
+)
+WAL_DECODE = (32, 240, 6320, 6336, 6384, 12464, 12480, 12528, 24752, 24768, 24944, 2414144)
+WAL_ENCODE = (2100320, 2100464, 2377792, 2378832, 2132336, 2163008, 2163024, 2164208, 2226752, 2226768, 2227952,
+              8200416)
 
 
 def test_write_batch_decode_workspace_bytes():
@@ -75,3 +96,19 @@ def test_sst_workspace_bytes(fn, want, at_limit):
     assert fn(MAX_CAP + 1, 0) == 0
     assert fn(0, MAX_BLOCK_CAP + 1) == 0
     assert fn(MAX_CAP + 1, MAX_BLOCK_CAP + 1) == 0
+
+
+def test_wal_scan_workspace_bytes():
+    assert tuple(tuple(LW.scan_workspace_bytes(b, c) for c in CAPS) for b in WAL_LOG_BYTES) == WAL_SCAN
+
+
+def test_wal_decode_workspace_bytes():
+    assert tuple(LW.decode_workspace_bytes(c) for c in CAPS) == WAL_DECODE
+    # the size function knows no limit (lv_wal_decode_device refuses scan_cap > 2^32 - 2)
+    assert LW.decode_workspace_bytes(MAX_CAP) == 103683194880
+    assert LW.decode_workspace_bytes(MAX_CAP + 1) == 103683194896
+
+
+def test_wal_encode_workspace_bytes():
+    assert tuple(LW.encode_workspace_bytes(f) for f in CAPS) == WAL_ENCODE
+    assert LW.encode_workspace_bytes(2**32 - 1) == 257701193792  # the most fragments of one call
