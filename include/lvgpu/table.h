@@ -70,8 +70,9 @@ int lv_sst_verify_blocks_host(const uint8_t *file, uint64_t file_bytes, const ui
  * The level-0 flush.  lv_sst_build_device walks the memtable
  * lv_memtable_build_device left in HBM (memtable.h) in d_order order and
  * writes a complete table file image into d_file: data blocks, a metaindex
- * block, an index block, every block's trailer, the footer.  Every entry is
- * written: shadowed versions, deletions and exact duplicates stay.
+ * block, an index block, every block's trailer, the footer.  Every entry of
+ * d_order is written: shadowed versions, deletions and exact duplicates stay
+ * unless lv_compact_filter_device (compact.h) took them out of the order.
  *
  * Parity.  The reference stops at table/format.rs (BlockHandle, Footer, the
  * magic number): it has no BlockBuilder, no TableBuilder and no
@@ -414,9 +415,12 @@ int lv_sst_get_host(const uint8_t *file, const lv_sst_table *table, const uint8_
  * what lv_memtable_build_device and lv_sst_build_device read, so a table can
  * be rewritten with other options, and several tables can be scanned into one
  * arena, sorted by the memtable build and flushed by the table build: a major
- * compaction that drops nothing.  The merging iterator as a streaming object,
- * dropping shadowed entries, several output files and version edits are not
- * part of this.  d_file may have any byte alignment.
+ * compaction.  What such a compaction drops (versions hidden behind a newer one
+ * that every snapshot sees, deletions with nothing beneath them) is
+ * lv_compact_filter_device's to decide, between the sort and the flush
+ * (compact.h); without it nothing is dropped.  The merging iterator as a
+ * streaming object, several output files and version edits are not part of
+ * this.  d_file may have any byte alignment.
  *
  * Output.  base_e / base_b are d_prev->entries / d_prev->arena_bytes, or 0
  * with a NULL d_prev.  Entry i of the table, in table order (index order, then

@@ -38,7 +38,8 @@
     defined(LVK_SB_COPY_LANES) || \
     defined(LVK_SS_TILE) || \
     defined(LVK_SS_WAVE_COPY) || \
-    defined(LVK_SS_COPY_LANES))
+    defined(LVK_SS_COPY_LANES) || \
+    defined(LVK_CF_TILE))
 #error "LVK_* kernel switches select untested code paths; only experiment variants (LVK_EXPERIMENT_BUILD, tools/build_variant.sh) may set them"
 #endif
 
@@ -116,4 +117,7 @@
 #endif
 #ifndef LVK_SS_COPY_LANES  // SSTable scan: lanes of a wave that share one such copy, a power of two <= 64 (r12, 100-byte values: 4 is 9 % faster than 16 on a 61 MB image and 1 % slower on a 244 MB one, 2 and 8 lie between; 32 and 64 are 22 % and 55 % slower)
 #define LVK_SS_COPY_LANES 4
+#endif
+#ifndef LVK_CF_TILE  // compaction filter: entries per scan tile of the flag kernel; a multiple of 256, at most 32,768 (the tile's four counts share one scanned word)
+#define LVK_CF_TILE 1024
 #endif

@@ -1,12 +1,13 @@
 // Device primitives shared by the pipeline stages (lvk/stage.h): WriteBatch
 // decode (write_batch.hip), memtable build and get (memtable.hip), SSTable
-// build (sst_build.hip), get (sst_get.hip) and scan (sst_scan.hip).
+// build (sst_build.hip), get (sst_get.hip) and scan (sst_scan.hip), the
+// compaction filter (compact.hip).
 //
 // The stages hand each other an op table (32-byte lv_wb_op entries over a
 // payload or an arena) and are built from the same few parts: an extent check
-// on what an op points at, the op as two 16-B accesses, a two-level scan
-// (tile-local in LDS, then one wave over the tiles' sums) and a copy of long
-// byte strings that the lanes of a wave share.  Each part is here once; the
+// on what an op points at, the op as two 16-B accesses, user keys compared as
+// bytes, a two-level scan (tile-local in LDS, then one wave over the tiles'
+// sums) and a copy of long byte strings that the lanes of a wave share.  Each part is here once; the
 // tile sizes, thread counts and copy knobs stay with the stage that owns them
 // and come in as template arguments.
 #pragma once
@@ -43,6 +44,45 @@ __device__ __forceinline__ void store_op(lv_wb_op *p, const lv_wb_op &o) {
     q[0] = u32x4{static_cast<uint32_t>(o.tag), static_cast<uint32_t>(o.tag >> 32), static_cast<uint32_t>(o.key_off),
                  static_cast<uint32_t>(o.key_off >> 32)};
     q[1] = u32x4{static_cast<uint32_t>(o.val_off), static_cast<uint32_t>(o.val_off >> 32), o.key_len, o.val_len};
+}
+
+// 8 bytes at any alignment as a big-endian word: all of them are key bytes.
+__device__ __forceinline__ uint64_t load_be64(const uint8_t *p) {
+    uint64_t v;
+    __builtin_memcpy(&v, p, 8);
+    return __builtin_bswap64(v);
+}
+
+// BytewiseComparator over a[0, alen) and b[0, blen): -1 / 0 / +1.  Whole
+// 8-byte words while both have them, then bytes: nothing outside is read.
+__device__ __forceinline__ int cmp_bytes(const uint8_t *a, uint64_t alen, const uint8_t *b, uint64_t blen) {
+    const uint64_t m = alen < blen ? alen : blen;
+    uint64_t i = 0;
+    for (; i + 8 <= m; i += 8) {
+        const uint64_t x = load_be64(a + i), y = load_be64(b + i);
+        if (x != y) return x < y ? -1 : 1;
+    }
+    for (; i < m; ++i) {
+        const uint32_t x = a[i], y = b[i];
+        if (x != y) return x < y ? -1 : 1;
+    }
+    return alen < blen ? -1 : alen > blen ? 1 : 0;
+}
+
+// a[0, alen) and b[0, blen) are the same bytes: the lengths first, then whole
+// 8-byte words at any alignment, then the rest.  Nothing outside is read.
+__device__ __forceinline__ bool same_bytes(const uint8_t *a, uint64_t alen, const uint8_t *b, uint64_t blen) {
+    if (alen != blen) return false;
+    uint64_t i = 0;
+    for (; i + 8 <= alen; i += 8) {
+        uint64_t x, y;
+        __builtin_memcpy(&x, a + i, 8);
+        __builtin_memcpy(&y, b + i, 8);
+        if (x != y) return false;
+    }
+    for (; i < alen; ++i)
+        if (a[i] != b[i]) return false;
+    return true;
 }
 
 // Inclusive scan of v over the 64 lanes of a wave.  Every lane of the wave

@@ -93,30 +93,8 @@ __device__ __forceinline__ uint64_t mt_entries(const MtArgs &A, uint32_t *status
     return n;
 }
 
-// 8 bytes at any alignment as a big-endian word: all of them are key bytes.
-__device__ __forceinline__ uint64_t mt_load_be(const uint8_t *p) {
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return __builtin_bswap64(v);
-}
-
-// BytewiseComparator over a[0, alen) and b[0, blen): -1 / 0 / +1.  Whole
-// 8-byte words while both have them, then bytes: nothing outside is read.
-__device__ __forceinline__ int mt_cmp_bytes(const uint8_t *a, uint64_t alen, const uint8_t *b, uint64_t blen) {
-    const uint64_t m = alen < blen ? alen : blen;
-    uint64_t i = 0;
-    for (; i + 8 <= m; i += 8) {
-        const uint64_t x = mt_load_be(a + i), y = mt_load_be(b + i);
-        if (x != y) return x < y ? -1 : 1;
-    }
-    for (; i < m; ++i) {
-        const uint32_t x = a[i], y = b[i];
-        if (x != y) return x < y ? -1 : 1;
-    }
-    return alen < blen ? -1 : alen > blen ? 1 : 0;
-}
-
-// -1 / 0 / +1 over the user keys of two entries.
+// -1 / 0 / +1 over the user keys of two entries (the byte compares are
+// lvk/stage.h's load_be64 and cmp_bytes).
 __device__ __forceinline__ int mt_cmp_keys(const MtArgs &A, const MtEnt &a, const MtEnt &b) {
 #pragma unroll
     for (uint32_t w = 0; w < kMtWords; ++w)
@@ -125,7 +103,7 @@ __device__ __forceinline__ int mt_cmp_keys(const MtArgs &A, const MtEnt &a, cons
     // other (zero padding: "a", "a\0" and "a\0\0" share a prefix): the length decides.
     if (a.klen <= kMtPrefix || b.klen <= kMtPrefix) return a.klen < b.klen ? -1 : a.klen > b.klen ? 1 : 0;
     const uint64_t ka = A.ops[a.idx].key_off, kb = A.ops[b.idx].key_off;
-    return mt_cmp_bytes(A.payload + ka + kMtPrefix, a.klen - kMtPrefix, A.payload + kb + kMtPrefix, b.klen - kMtPrefix);
+    return cmp_bytes(A.payload + ka + kMtPrefix, a.klen - kMtPrefix, A.payload + kb + kMtPrefix, b.klen - kMtPrefix);
 }
 
 // The strict total order.  Padding entries come after every op.
@@ -177,7 +155,7 @@ __global__ __launch_bounds__(kMtThreads) void mt_tile_sort(const MtArgs A) {
                 for (uint32_t w = 0; w < kMtWords; ++w) {
                     uint64_t v = 0;
                     if (have >= 8 * w + 8) {
-                        v = mt_load_be(k + 8 * w);
+                        v = load_be64(k + 8 * w);
                     } else {
                         for (uint32_t b = 8 * w; b < have; ++b) v |= static_cast<uint64_t>(k[b]) << (56 - 8 * (b & 7u));
                     }
@@ -361,7 +339,7 @@ __global__ __launch_bounds__(kMtThreads) void mt_get(const MtGetArgs G) {
                 ok = false;
                 break;
             }
-            const int c = mt_cmp_bytes(G.payload + o.key_off, o.key_len, qk, ql);
+            const int c = cmp_bytes(G.payload + o.key_off, o.key_len, qk, ql);
             if (c < 0 || (c == 0 && o.tag > qtag))
                 lo = mid + 1;
             else
@@ -373,7 +351,7 @@ __global__ __launch_bounds__(kMtThreads) void mt_get(const MtGetArgs G) {
             const uint32_t idx = G.order[lo];
             const lv_wb_op o = load_op(G.ops + idx);
             if (extent_ok(o.key_off, o.key_len, G.payload_bytes) &&
-                mt_cmp_bytes(G.payload + o.key_off, o.key_len, qk, ql) == 0) {
+                cmp_bytes(G.payload + o.key_off, o.key_len, qk, ql) == 0) {
                 r.op = idx;
                 if ((o.tag & 0xffu) == LV_WB_TYPE_VALUE) {
                     r.status = LV_MT_GET_FOUND;
