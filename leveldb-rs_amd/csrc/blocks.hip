@@ -34,7 +34,9 @@ __global__ __launch_bounds__(kThreads) void crc32c_batch_kernel(Params P, const 
 // is wave-uniform (scalar), there is no head/tail work, and the seed enters
 // as lane 0's first word.  Every row ends on the block's last batch, so the
 // rows' registers are carried from batch to batch through the jump table of
-// the blocks images (fold_batch_carry; `last` = the block's last batch).
+// the blocks images (fold_batch_carry; `last` = the block's last batch), and
+// that last batch leaves the registers of a sub-group of lanes at one common
+// end point, so the rows and lanes join by XOR and a few shifts (join_group).
 // Every step issues the SAME loads (next batch, and for seeded calls the
 // next block's seed) whether or not a next batch exists -- the last one
 // reads the arena's first row.  The compiler's s_waitcnt counts are static:
@@ -192,7 +194,7 @@ __global__ __launch_bounds__(kThreads) void crc32c_blocks_kernel(Params P, uint3
             if (nb > 1) fold_batch_carry(v1, A, L, nb == 2);
             if (nb > 2) fold_batch_carry(v2, A, L, nb == 3);
             if (nb > 3) fold_batch_carry(v3, A, L, nb == 4);
-            const uint32_t X = merge_group<G, -1, -1, true>(A, L);
+            const uint32_t X = join_group<G>(A, lane);
             if constexpr (FUSE) {
                 if (gl == 0) g_ocrc[wave][lane / G] = X;
                 fuse_pieces(P, fm, g_ocrc, lane, wave);
@@ -238,11 +240,16 @@ __global__ __launch_bounds__(kThreads) void crc32c_blocks_kernel(Params P, uint3
 #pragma unroll
         for (uint32_t i = 0; i < U; ++i) nxt[i] = load16(lptr + kRow * i);
         if (j == 0 && gl == 0) cur[0].x ^= s0;
-        fold_batch_carry(cur, A, L, lastj);
-        if (lastj) {
+        // one wave-uniform branch around the last slice step and the join
+        uint32_t sl[U];
+        carry_slices(cur, A, L, sl);
+        if (!lastj) {
+            carry_finish<false>(sl, A, L);
+        } else {
+            carry_finish<true>(sl, A, L);
             // round r's K results -> LDS slot (r % G)*K + group; one store of
             // the wave's 64 slots every G rounds (and after the last round)
-            const uint32_t X = merge_group<G, -1, -1, true>(A, L);
+            const uint32_t X = join_group<G>(A, lane);
 #pragma unroll
             for (uint32_t i = 0; i < U; ++i) A[i] = 0u;
             if (gl == 0) g_ocrc[wave][(r % G) * kGroups + lane / G] = PIECES ? X : final_crc(P, X);

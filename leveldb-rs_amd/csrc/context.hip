@@ -93,6 +93,35 @@ const std::vector<uint32_t> &host_image(int gi) {
             for (int e = 0; e < 256; ++e)
                 for (int c = 0; c < 8; ++c)
                     for (int k = 0; k < 4; ++k) rj[e * 64 + 32 + 4 * c + k] = J[3 - k][e];
+            // Region B: the last batch's positioned slice step.  Copy c is
+            // read by the lanes l = c (mod w) of a sub-group of w = min(G, 8)
+            // lanes and holds E0 = Shift_{4 + d}, E1 = Shift_{4 + 32G + d},
+            // d = 16 (w - 1 - c mod w): the bytes from the lane's granule to
+            // the sub-group's last one (of row 2 for rows 0 and 2, E1 / E0; of
+            // row 3 for rows 1 and 3).
+            const uint64_t G = static_cast<uint64_t>(kGs[i]), w = G < 8 ? G : 8;
+            uint32_t *rb = &images[kBlocksImage + i][lvk::kRegionB / 4];
+            for (uint64_t c = 0; c < 8; ++c) {
+                uint32_t E0[4][256], E1[4][256];
+                const uint64_t d = 16 * (w - 1 - c % w);
+                lvgpu::shift_tables(4 + d, E0);
+                lvgpu::shift_tables(4 + 32 * G + d, E1);
+                for (int e = 0; e < 256; ++e)
+                    for (int k = 0; k < 4; ++k) {
+                        rb[e * 64 + 4 * c + k] = E0[3 - k][e];
+                        rb[e * 64 + 32 + 4 * c + k] = E1[3 - k][e];
+                    }
+            }
+            // Combine slots: the shifts of that G's join (lvk::join_group).
+            static const uint64_t kJoin[4][4] = {{16, 0, 0, 0}, {64, 0, 0, 0}, {128, 256, 384, 0}, {1024, 128, 256, 512}};
+            uint32_t *rc = &images[kBlocksImage + i][lvk::kComb / 4];
+            std::fill(rc, rc + 6 * 1024, 0u);
+            for (int k = 0; k < 4 && kJoin[i][k]; ++k) {
+                uint32_t S[4][256];
+                lvgpu::shift_tables(kJoin[i][k], S);
+                for (int j = 0; j < 4; ++j)
+                    for (int e = 0; e < 256; ++e) rc[(k * 4 + j) * 256 + e] = S[j][e];
+            }
         }
     });
     return images[gi];

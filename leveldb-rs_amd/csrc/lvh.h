@@ -51,7 +51,9 @@ constexpr int kAlImage = kAlRowsH == 4 ? 2 : kTableImage;
 static_assert(kAlRowsH == 4 || kAlRowsH == lvk::kSstRows, "aligned rows: 4, or the table image's");
 // The uniform-block kernel's images, one per G (kBlocksImage + index into
 // kGs): the per-G image with region A's row shift replaced by the carried
-// fold's jump Shift_{16*G*U - 12} (lvk::fold_batch_carry).
+// fold's jump Shift_{16*G*U - 12}, region B by the last batch's positioned
+// tables E0 / E1 (per-copy contents) and the combine slots by the join's
+// shifts (lvk::fold_batch_carry, lvk::join_group).
 constexpr int kBlocksImage = 5;
 constexpr int kImages = 9;
 

@@ -22,7 +22,11 @@
 //    end on a block's last batch, carries A_i instead (fold_batch_carry): the
 //    last slice step of a granule reads J = Shift_{16GU-12} in place of
 //    T = Shift_4 and the result enters the next batch's first word, so the
-//    row shift costs no lookup of its own.
+//    row shift costs no lookup of its own.  On the block's last batch that
+//    step reads a table that differs per lane of a sub-group (region B of the
+//    blocks images) and already holds the shift to the sub-group's last
+//    granule, so rows and lanes join by XOR and only 2 partials per 8 lanes
+//    are shifted (join_group): 260 lookups per lane and 4 KiB block.
 //  * The seed enters by xoring (seed ^ ~0) into the first 4 buffer bytes:
 //    R(s, w||D) = R(0, (s^w)||D).  Buffers shorter than 4 bytes go bytewise.
 //  * Lookup tables live in LDS.  The slice tables T0..T3 and the row-shift
@@ -57,6 +61,13 @@ constexpr uint32_t U = 4;       // rows per batch (= interleaved Horner accumula
 //                 kernel's images hold J = Shift_{16*G*U - 12} there
 //   [64K, 128K)   region B: dwords 0..31 W1 = Shift_{16*G}, 32..63 W2 = Shift_{32*G}
 //   [128K, 152K)  combine tables Shift_{16*2^k}, k = 0..5, plain byte tables
+// The blocks kernel's images differ in regions B and C:
+//   region B      dwords 0..31 E0, 32..63 E1, the last batch's positioned slice
+//                 step; copy c holds E0_c = Shift_{4 + 16(w-1 - c mod w)} and
+//                 E1_c = Shift_{32*G} o E0_c, w = min(G, 8) (fold_batch_carry)
+//   combine slots the join's shifts (join_group): G = 1 Shift_16; G = 4
+//                 Shift_64; G = 16 Shift_128, Shift_256, Shift_384; G = 64
+//                 Shift_1024, Shift_128, Shift_256, Shift_512; the rest zero
 constexpr uint32_t kRegionA = 0;
 constexpr uint32_t kRegionB = 65536;
 constexpr uint32_t kHalf = 128;  // second table set of a region: +32 dwords
@@ -238,28 +249,78 @@ __device__ __forceinline__ void fold_batch(const uint4 (&v)[NU], uint32_t (&A)[N
 // as the register just before this batch's granule (xored into its first
 // word; 0 at a block's first batch) and leaves as the register just before
 // the next batch's -- the last slice step reads J instead of T = Shift_4, so
-// the row shift costs no lookup of its own -- or, on the block's LAST batch
-// (T), as R at the end of the granule, which is what merge_group takes.
-// `last` is wave-uniform.  J sits kHalf bytes after T in every row and the
-// lane's dword offsets are < kHalf, so the J address is the T address with
-// bit 7 of the offset byte set: one select per batch, no second body.
+// the row shift costs no lookup of its own.  `last` (the block's last batch)
+// is wave-uniform.  J sits kHalf bytes after T in every row and the lane's
+// dword offsets are < kHalf, so the J address is the T address with bit 7 of
+// the offset byte set.
+//
+// The block's last batch is POSITIONED: its last slice step reads region B,
+// whose eight copies differ.  Copy c -- the one lane l = c (mod 8) reads --
+// holds E0_c = Shift_{4 + 16 (w-1-c mod w)} and, kHalf on, E1_c = Shift_{32G}
+// o E0_c (w = min(G, 8) lanes per sub-group).  Rows 2-3 read E0 and rows 0-1
+// E1, so the w lanes of a sub-group leave rows 0 and 2 at the end of the
+// sub-group's last granule of row 2 and rows 1 and 3 at that of row 3, and
+// they join by plain XOR (join_group).  Region B starts at address bit 16,
+// which the 16-bit offset field of a DS read cannot add: the last batch's
+// v_perm takes it from a 0x01 byte of its table-offset operand (LutE), so
+// neither path pays a VALU add.  The two paths are a wave-uniform branch
+// around the last slice step only; steps 0-2 are one body.
+struct LutE {
+    uint32_t lv01, lv23;  // S1 of lookups 0-1 / 2-3: their offset bytes and a 0x01
+    uint32_t sel0, sel1, sel2, sel3;
+};
+static_assert(kRegionB == 0x10000u, "LutE sets address bit 16");
+
+__device__ __forceinline__ LutE make_lute(const Lut &L) {
+    LutE E;
+    E.lv01 = (L.lv & 0x0000ffffu) | 0x01010000u;
+    E.lv23 = (L.lv & 0xffff0000u) | 0x00000101u;
+    // address byte 2: S1 byte 3 (lookups 0-1) or S1 byte 0 (lookups 2-3)
+    E.sel0 = (L.sel0 & 0xff00ffffu) | 0x00030000u;
+    E.sel1 = (L.sel1 & 0xff00ffffu) | 0x00030000u;
+    E.sel2 = L.sel2 & 0xff00ffffu;
+    E.sel3 = L.sel3 & 0xff00ffffu;
+    return E;
+}
+
+// The last slice step of a batch's granules: A[i] = table(s[i]), rows below
+// NU / 2 at OFF_LO and the others at OFF_HI from the v_perm address.
+template <uint32_t NU, uint32_t OFF_LO, uint32_t OFF_HI>
+__device__ __forceinline__ void carry_last_step(const uint32_t (&s)[NU], uint32_t (&A)[NU], uint32_t lv01,
+                                                uint32_t lv23, uint32_t sel0, uint32_t sel1, uint32_t sel2,
+                                                uint32_t sel3) {
+    uint32_t ad[NU][4];
+#pragma unroll
+    for (uint32_t i = 0; i < NU; ++i) {
+        ad[i][0] = __builtin_amdgcn_perm(s[i], lv01, sel0);
+        ad[i][1] = __builtin_amdgcn_perm(s[i], lv01, sel1);
+        ad[i][2] = __builtin_amdgcn_perm(s[i], lv23, sel2);
+        ad[i][3] = __builtin_amdgcn_perm(s[i], lv23, sel3);
+    }
+    uint32_t t[NU][4];
+#pragma unroll
+    for (uint32_t i = 0; i < NU; ++i)
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) t[i][k] = lds_word(ad[i][k] + (i < NU / 2 ? OFF_LO : OFF_HI));
+#pragma unroll
+    for (uint32_t i = 0; i < NU; ++i) A[i] = xor3(t[i][0], t[i][1], t[i][2]) ^ t[i][3];
+}
+
+// Slice steps 0-2 of a batch's granules: s[i] is the state before the last step.
 template <uint32_t NU = U>
-__device__ __forceinline__ void fold_batch_carry(const uint4 (&v)[NU], uint32_t (&A)[NU], const Lut &L, bool last) {
-    Lut L3 = L;
-    L3.lv = last ? L.lv : L.lv | 0x80808080u;
-    uint32_t s[NU];
+__device__ __forceinline__ void carry_slices(const uint4 (&v)[NU], const uint32_t (&A)[NU], const Lut &L,
+                                             uint32_t (&s)[NU]) {
 #pragma unroll
     for (uint32_t i = 0; i < NU; ++i) s[i] = v[i].x ^ A[i];
 #pragma unroll
-    for (uint32_t step = 0; step < 4; ++step) {
-        const Lut &Ls = step < 3 ? L : L3;
+    for (uint32_t step = 0; step < 3; ++step) {
         uint32_t ad[NU][4];
 #pragma unroll
         for (uint32_t i = 0; i < NU; ++i) {
-            ad[i][0] = lut_addr<0>(s[i], Ls);
-            ad[i][1] = lut_addr<1>(s[i], Ls);
-            ad[i][2] = lut_addr<2>(s[i], Ls);
-            ad[i][3] = lut_addr<3>(s[i], Ls);
+            ad[i][0] = lut_addr<0>(s[i], L);
+            ad[i][1] = lut_addr<1>(s[i], L);
+            ad[i][2] = lut_addr<2>(s[i], L);
+            ad[i][3] = lut_addr<3>(s[i], L);
         }
         uint32_t t[NU][4];
 #pragma unroll
@@ -268,15 +329,36 @@ __device__ __forceinline__ void fold_batch_carry(const uint4 (&v)[NU], uint32_t 
             for (uint32_t k = 0; k < 4; ++k) t[i][k] = lds_word(ad[i][k] + kRegionA);
 #pragma unroll
         for (uint32_t i = 0; i < NU; ++i) {
-            const uint32_t x = xor3(t[i][0], t[i][1], t[i][2]);
-            if (step < 3) {
-                const uint32_t nw = step == 0 ? v[i].y : step == 1 ? v[i].z : v[i].w;
-                s[i] = xor3(x, t[i][3], nw);
-            } else {
-                A[i] = x ^ t[i][3];
-            }
+            const uint32_t nw = step == 0 ? v[i].y : step == 1 ? v[i].z : v[i].w;
+            s[i] = xor3(xor3(t[i][0], t[i][1], t[i][2]), t[i][3], nw);
         }
     }
+}
+
+// The last slice step: positioned (region B) on a block's last batch, the
+// jump J otherwise.  A caller with more to do on the last batch branches on
+// `last` once, around this step and its own work (the blocks kernel's step).
+template <bool LAST, uint32_t NU = U>
+__device__ __forceinline__ void carry_finish(const uint32_t (&s)[NU], uint32_t (&A)[NU], const Lut &L) {
+    static_assert(NU == U, "region B positions the four rows of a batch");
+    if constexpr (LAST) {
+        const LutE E = make_lute(L);
+        carry_last_step<NU, kRegionB - 0x10000u + kHalf, kRegionB - 0x10000u>(s, A, E.lv01, E.lv23, E.sel0, E.sel1,
+                                                                              E.sel2, E.sel3);
+    } else {  // J: the T address with bit 7 of the offset byte set
+        const uint32_t lvj = L.lv | 0x80808080u;
+        carry_last_step<NU, kRegionA, kRegionA>(s, A, lvj, lvj, L.sel0, L.sel1, L.sel2, L.sel3);
+    }
+}
+
+template <uint32_t NU = U>
+__device__ __forceinline__ void fold_batch_carry(const uint4 (&v)[NU], uint32_t (&A)[NU], const Lut &L, bool last) {
+    uint32_t s[NU];
+    carry_slices(v, A, L, s);
+    if (last)
+        carry_finish<true>(s, A, L);
+    else
+        carry_finish<false>(s, A, L);
 }
 
 // One byte through T0 (this lane's copy): crc32c.rs:81.
@@ -655,6 +737,79 @@ __device__ __forceinline__ uint32_t merge_group(const uint32_t (&A)[U], const Lu
         X = comb_shift(X, k) ^ other;
     }
     return X;
+}
+
+// x of lane l + N (row_shl) or l - N (row_shr) of the 16-lane DPP row; lanes
+// past the row's end read 0.
+template <uint32_t N>
+__device__ __forceinline__ uint32_t row_up(uint32_t x) {
+    return __builtin_amdgcn_mov_dpp(x, 0x100 + N, 0xf, 0xf, true);
+}
+template <uint32_t N>
+__device__ __forceinline__ uint32_t row_down(uint32_t x) {
+    return __builtin_amdgcn_mov_dpp(x, 0x110 + N, 0xf, 0xf, true);
+}
+
+// Shift(a) from the plain byte tables at LDS byte address tb (lane-varying).
+__device__ __forceinline__ uint32_t comb_shift_at(uint32_t a, uint32_t tb) {
+    return xor3(lds_word(tb + (a & 0xffu) * 4u), lds_word(tb + 1024u + ((a >> 8) & 0xffu) * 4u),
+                lds_word(tb + 2048u + ((a >> 16) & 0xffu) * 4u)) ^
+           lds_word(tb + 3072u + (a >> 24) * 4u);
+}
+
+// The join of the uniform-block kernel after a positioned last batch
+// (fold_batch_carry): lane 0 of the group returns R(~seed, block).
+// Rows 0 and 2 of a sub-group's w = min(G, 8) lanes end at one point and rows
+// 1 and 3 at another, 16G bytes on, so with y_m / z_m the XOR of A0 ^ A2 /
+// A1 ^ A3 over sub-group m (DPP moves, no LDS):
+//   X = XOR_m Shift_{16w (M-1-m)}( Shift_{16G}(y_m) ^ z_m ),  M = G / w.
+// The sums land in the sub-group's first two lanes (y in lane 0 by a tree
+// towards lower lanes, z in lane 1: its first level pairs towards the odd
+// lane).  The shifts read the blocks image's combine slots:
+//   G = 1, 4: Shift_{16G}(y) ^ z, slot 0.
+//   G = 16:   X = Shift_384(y_0) ^ Shift_128(z_0) ^ Shift_256(y_1) ^ z_1 with
+//             y_0, z_0, y_1 in lanes 0, 1, 8, each reading its own table
+//             (slots 2, 0, 1) in ONE lookup: 4 LDS reads per lane and block.
+//   G = 64:   v_m = Shift_1024(y_m) ^ z_m (slot 0), then a tree over the
+//             octets with Shift_128, Shift_256, Shift_512 (slots 1-3).
+// Lanes that hold no partial look up 0 -- one address for all of them, a
+// broadcast in place of bank conflicts -- and Shift(0) = 0 keeps them out of
+// the XORs.
+template <int G>
+__device__ __forceinline__ uint32_t join_group(const uint32_t (&A)[U], uint32_t lane) {
+    const uint32_t y = A[0] ^ A[2], z = A[1] ^ A[3];
+    if constexpr (G == 1) {
+        return comb_shift_at(y, kComb) ^ z;
+    } else {
+        // q: lane 0 of a sub-group y_m, lane 1 z_m
+        // (both moves run with every lane enabled: a DPP read of a disabled lane is 0)
+        const uint32_t yp = y ^ row_up<1>(y), zp = z ^ row_down<1>(z);
+        uint32_t q = (lane & 1u) ? zp : yp;
+        q ^= row_up<2>(q);
+        if constexpr (G >= 8) q ^= row_up<4>(q);
+        if constexpr (G == 16) {
+            const uint32_t gl = lane & 15u;
+            const bool part = gl <= 1u || gl == 8u;
+            const uint32_t tb = kComb + (gl == 0u ? 2u * 4096u : gl == 8u ? 4096u : 0u);
+            uint32_t r = comb_shift_at(part ? q : 0u, tb);
+            r ^= row_up<1>(r);
+            r ^= row_up<8>(r);
+            return r ^ row_up<9>(q);
+        } else {
+            constexpr uint32_t w = G < 8 ? G : 8;
+            const bool first = (lane & (w - 1u)) == 0u;
+            uint32_t X = comb_shift_at(first ? q : 0u, kComb) ^ row_up<1>(q);
+            if constexpr (G == 64) {
+                X = first ? X : 0u;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const uint32_t other = lanes_down<G, true>(X, 3 + k);
+                    X = comb_shift_at(X, kComb + (1u + k) * 4096u) ^ other;
+                }
+            }
+            return X;
+        }
+    }
 }
 
 __device__ __forceinline__ uint32_t final_crc(const Params &P, uint32_t X) {
