@@ -86,7 +86,9 @@ int lv_sst_verify_blocks_host(const uint8_t *file, uint64_t file_bytes, const ui
  * and lv_sst_get_device, below), which opens and reads every table it writes.
  *
  * Options: block_size (default 4096), restart_interval (default 16); no
- * compression (type byte 0), no filter policy.  A NULL opt means the defaults.
+ * compression (type byte 0), no filter policy (lv_sst_build_bloom_device,
+ * "Bloom filter blocks" below, is the build with one).  A NULL opt means the
+ * defaults.
  *
  * An entry's key is the internal key: the user key, then the tag as 8
  * little-endian bytes.
@@ -545,6 +547,211 @@ int lv_sst_scan_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_ta
 int lv_sst_scan_host(const uint8_t *file, const lv_sst_table *table, const lv_sst_scan_totals *prev,
                      uint8_t *arena, uint64_t arena_cap, lv_wb_op *ops, size_t op_cap,
                      uint32_t *order, lv_mt_totals *mt_totals, lv_sst_scan_totals *totals);
+
+/* ---- Bloom filter blocks: the build with a filter policy, and a filtered Get --
+ *
+ * lv_sst_build_bloom_device is lv_sst_build_device with upstream's
+ * NewBloomFilterPolicy(bits_per_key): the image gains a filter block and a
+ * metaindex block that names it.  lv_sst_bloom_open_device finds the filter of
+ * an opened image (Table::ReadMeta / ReadFilter) and lv_sst_get_bloom_device
+ * is lv_sst_get_device asking it before it touches a data block, so a lookup
+ * of a key the table does not hold usually stops after the index seek.
+ * lv_sst_build_device, lv_sst_open_device, lv_sst_get_device and
+ * lv_sst_scan_device are unchanged, and they and lv_sst_verify_blocks_device
+ * take a bloom image as it is: a reader without a filter policy ignores the
+ * metaindex entry.
+ *
+ * Parity.  The reference has no filter policy at all.  The filter, the filter
+ * block and the metaindex entry below are therefore upstream C++ LevelDB's
+ * (util/bloom.cc, table/filter_block.cc, table/table_builder.cc,
+ * table/table.cc), as the block and index layout (above) and the trailer's
+ * are.  No LevelDB library was available to open an image, so "a stock LevelDB
+ * opens it" is UNPINNED.  What pins the format: the worked example below
+ * (tests/golden/sst_bloom_one_entry.json), the reference's own KAT of the hash
+ * at the Bloom seed (hash([0x62], 0xbc9f1d34) == 0xef1345c4), an independent
+ * Python model with a reader (tests/sst_bloom_cases.py) and the project's own
+ * reader.
+ *
+ * Bloom filter over n keys at bits_per_key = bpk.
+ *   k = min(30, max(1, bpk * 69 / 100)) in integers (upstream's
+ *   (size_t)(bpk * 0.69) clamped to [1, 30]; equal for every bpk below 300).
+ *   bits = max(64, n * bpk); bytes = (bits + 7) / 8; bits = 8 * bytes.  The
+ *   filter is `bytes` zero bytes, then the byte k.  For each key:
+ *   h = lv_hash(key, 0xbc9f1d34), delta = rotr32(h, 17); k times: set bit
+ *   h % bits (byte pos / 8, bit pos % 8), h += delta (u32 wrap).
+ *   A key is a USER key (upstream's InternalFilterPolicy strips the tag), and
+ *   every entry adds its key: versions and exact duplicates count in n.
+ *   key_may_match(key, filter): len < 2: false.  k = the last byte; k > 30:
+ *   true.  bits = 8 (len - 1); probe as above; a clear bit: false.
+ *
+ * Filter block (FilterBlockBuilder, base lg LV_SST_FILTER_BASE_LG = 11).  A
+ * data block that starts at file offset o belongs to window o >> 11.  Filter f
+ * is the Bloom filter over the entries of all data blocks of window f, in
+ * order; if there are none it is zero bytes, not an empty Bloom filter.
+ * Serially: StartBlock(0) at the start; after each data block is written,
+ * StartBlock(next offset) runs GenerateFilter while offset / 2048 > filters so
+ * far; at finish one more GenerateFilter runs if keys are pending.  The filter
+ * count is therefore F = max((last block's offset >> 11) + 1, data_end >> 11)
+ * with data_end the offset behind the last data block's trailer.  Contents:
+ * the F filters end to end, F fixed32 start offsets, fixed32 array_offset (the
+ * filters' total size), the byte 11.  It is written raw at data_end with type
+ * 0 and the usual trailer.
+ *
+ * Metaindex: a BlockBuilder with the table's restart_interval holding the one
+ * entry LV_SST_BLOOM_NAME (34 bytes) -> the handle encoding of the filter
+ * block.  Order in the file: data blocks, filter block, metaindex, index,
+ * footer.
+ *
+ * Worked example: key "k", sequence 1, VALUE, value "v", defaults, bpk 10.
+ * lv_hash("k", 0xbc9f1d34) = 0xeadd29bc, k = 6.
+ *   [0,21)    the data block of the example above      [21,26)  its trailer
+ *   [26,44)   filter block 40 00 00 01 04 04 10 10 06 | 00 00 00 00 |
+ *             09 00 00 00 | 0b                          [44,49)  its trailer
+ *   [49,96)   metaindex 00 22 02, the 34 name bytes, 1a 12 | 00 00 00 00 |
+ *             01 00 00 00                               [96,101) its trailer
+ *   [101,123) the index block, as above                [123,128) its trailer
+ *   [128,176) footer 31 2f 65 16, zero padding to 40 bytes, the magic
+ *
+ * lv_sst_build_bloom_device takes lv_sst_build_device's arguments, with the
+ * same checks, and bloom != NULL with 1 <= bits_per_key <= 64 and reserved ==
+ * 0 (LV_ERR_INVALID otherwise).  *d_totals is written as there, its metaindex
+ * fields naming the metaindex block that holds the entry; *d_bloom_totals
+ * (8-byte aligned, always written) is {filter_offset, filter_size, filters,
+ * filter_keys}: the filter block's handle, F and the keys added (= entries);
+ * all 0 unless the status is 0 and entries != 0.  d_handles receives
+ * data_blocks + 3 pairs: the data blocks, the filter block, the metaindex
+ * block, the index block; the caller provides room for block_cap + 3 pairs,
+ * and lv_sst_verify_blocks_device takes them unchanged.  The four statuses are
+ * lv_sst_build_device's, decided once in the plan before any byte is written;
+ * BLOCK_LARGE also when the filter block's size reaches 2^32 - 1 (all filter
+ * sizes are u64).  file_bytes, metaindex_* and index_* are the true ones under
+ * HANDLE_OVER and FILE_OVER.  An empty memtable writes nothing.
+ *
+ * lv_sst_build_bloom_file_bound: lv_sst_build_file_bound plus
+ *   filters        a non-empty filter over n_w keys is max(8, ceil(n_w bpk / 8))
+ *                  + 1 <= n_w bpk / 8 + 9 bytes; the n_w sum to n and there
+ *                  are at most n of them (one per block): n bpk / 8 + 1 + 9 n;
+ *   offsets        4 per window; data_end <= payload_bytes + 36 n (the data
+ *                  entries' and blocks' terms above), F <= data_end / 2048 + 1:
+ *                  (payload_bytes + 36 n) / 512 + 4;
+ *   array_offset, the base byte and the trailer: 10;
+ *   metaindex      3 + 34 + at most 20 of handle + 8, against the 8 counted: 57
+ * so the bound is 2 payload_bytes + 75 n + 70 + n bpk / 8 + 9 n +
+ * (payload_bytes + 36 n) / 512 + 72 (saturating; 0 for op_cap == 0 or a bad
+ * bloom).
+ *
+ * Launch sequence.  lv_sst_build_device's, with two launches added before
+ * the plan (per data block its window, whether it is the window's first, the
+ * window's key count and filter size with a tile scan; the tile carries) and
+ * three behind the entry emit: the filter emit, a wave per non-empty filter in
+ * a grid-stride loop over the data blocks, which zeroes the filter's bits in
+ * LDS, has its lanes hash the window's user keys and OR their k bits in with
+ * LDS atomics, and stores the bytes with plain stores of the destination's
+ * alignment (a filter beyond the wave's LDS budget is zero-filled instead);
+ * the large-filter kernel, which sets such a filter's bits with atomic ORs on
+ * aligned dwords of d_file and stores nothing else; and the offsets kernel, a
+ * lane per window.  Bit OR is order-free, so the image is bit-exact however
+ * the lanes are scheduled.  The seal covers the data blocks and the metaindex
+ * block; the filter block, which grows with the table, joins the index block
+ * in the one lv_crc32c_batch_device_ws call as a second buffer.  The grids
+ * depend on op_cap, block_cap and file_cap only.  No workgroup waits on
+ * another.  Capturable like the build. */
+#define LV_SST_BLOOM_NAME "filter.leveldb.BuiltinBloomFilter2"
+#define LV_SST_FILTER_BASE_LG 11u
+#define LV_SST_BLOOM_SEED 0xbc9f1d34u
+typedef struct lv_sst_bloom_options { uint32_t bits_per_key, reserved; } lv_sst_bloom_options;
+typedef struct lv_sst_bloom_totals {     /* device memory, 8-B aligned, always written */
+    uint64_t filter_offset, filter_size, filters, filter_keys;
+} lv_sst_bloom_totals;
+
+/* Host scalars (pure).  lv_bloom_hash is lv_hash at the Bloom seed.
+ * lv_bloom_filter_bytes(n, bpk) is the filter's size with its k byte (0 for
+ * bpk == 0).  lv_bloom_create_filter builds the filter over the n keys
+ * keys[off[i], off[i] + len[i]) into dst[0, lv_bloom_filter_bytes(n, bpk)):
+ * LV_OK, or LV_ERR_INVALID for a NULL pointer the call needs or bpk == 0. */
+uint32_t lv_bloom_hash(const uint8_t *key, size_t n);
+size_t lv_bloom_filter_bytes(size_t n, uint32_t bits_per_key);
+int lv_bloom_create_filter(const uint8_t *keys, const uint64_t *off, const uint32_t *len, size_t n,
+                           uint32_t bits_per_key, uint8_t *dst);
+int lv_bloom_key_may_match(const uint8_t *key, size_t key_len, const uint8_t *filter, size_t filter_len);
+
+size_t lv_sst_build_bloom_workspace_bytes(size_t op_cap, size_t block_cap);
+uint64_t lv_sst_build_bloom_file_bound(uint64_t payload_bytes, uint64_t op_cap, const lv_sst_build_options *opt,
+                                       const lv_sst_bloom_options *bloom);
+int lv_sst_build_bloom_device(const uint8_t *d_payload, size_t payload_bytes, const lv_wb_op *d_ops,
+                              const uint32_t *d_order, const lv_mt_totals *d_mt_totals, size_t op_cap,
+                              const lv_sst_build_options *opt, const lv_sst_bloom_options *bloom,
+                              uint8_t *d_file, uint64_t file_cap, uint64_t *d_handles, size_t block_cap,
+                              lv_sst_build_totals *d_totals, lv_sst_bloom_totals *d_bloom_totals, uint32_t flags,
+                              void *d_workspace, size_t workspace_bytes, void *stream);
+/* The host twin (pure, no GPU), with lv_sst_build_host's sizing-pass rule and
+ * return values; handles has room for block_cap + 3 pairs. */
+int lv_sst_build_bloom_host(const uint8_t *payload, size_t payload_bytes, const lv_wb_op *ops,
+                            const uint32_t *order, const lv_mt_totals *mt_totals,
+                            const lv_sst_build_options *opt, const lv_sst_bloom_options *bloom,
+                            uint8_t *file, uint64_t file_cap, uint64_t *handles, size_t block_cap,
+                            lv_sst_build_totals *totals, lv_sst_bloom_totals *bloom_totals);
+
+/* Reader (FilterBlockReader, Table::ReadMeta / ReadFilter, InternalGet).  Any
+ * failure to find or parse the filter means "no filter"; it is never an error.
+ *   ReadMeta.  The metaindex handle of *d_table is range-checked, its type
+ *   byte must be 0 and its restart header sound (BAD_METAINDEX).  The first
+ *   entry whose key is not less than LV_SST_BLOOM_NAME bytewise is found by a
+ *   linear walk from offset 0 with limit arr (decode, above; a failed decode
+ *   or shared > the previous key's length: BAD_METAINDEX); none, or a key
+ *   other than the name: NO_ENTRY.  Its value must begin with a handle that is
+ *   in range (BAD_HANDLE) and whose type byte is 0 (BAD_TYPE).  Filter
+ *   contents of n < 5 bytes: SHORT; array_offset = LE32 at n - 5 > n - 5:
+ *   BAD_ARRAY.  num = (n - 5 - array_offset) / 4; base_lg = the last byte.
+ *   may_match(block_offset, key).  i = block_offset >> base_lg (0 for a shift
+ *   of 64 or more).  i >= num: true.  start, limit = LE32 at array + 4 i and
+ *   array + 4 i + 4.  start <= limit <= array_offset: key_may_match over
+ *   [start, limit).  Otherwise start == limit: false.  Otherwise true.
+ *
+ * lv_sst_bloom_open_device writes *d_bloom (8-byte aligned, every field) from
+ * the image and the *d_table lv_sst_open_device wrote, read on the device.
+ * {filter_offset, filter_size} is a handle pair lv_sst_verify_blocks_device
+ * takes with n = 1.  present is 0 or 1; why is 0 with a filter and otherwise
+ * the first reason there is none, in this order: TABLE (d_table->status != 0
+ * or its file_bytes > file_cap), EMPTY (file_bytes == 0), then ReadMeta's.
+ * One one-thread launch, stream-ordered, capturable.  Arguments (LV_ERR_INVALID):
+ * NULL d_table or d_bloom, NULL d_file with file_cap != 0, either not 8-byte
+ * aligned, flags != 0.
+ *
+ * lv_sst_get_bloom_device is lv_sst_get_device plus d_bloom, read on the
+ * device in stream order (NULL or misaligned: LV_ERR_INVALID).  With present
+ * == 0 the results are byte for byte lv_sst_get_device's.  With a filter it is
+ * asked after the index seek has produced a handle that is in range and before
+ * anything of the data block is read: a query it rejects gets ABSENT with
+ * every other field 0 and reserved = LV_SST_GET_FILTERED; every other query
+ * gets what lv_sst_get_device gives.  Every offset taken from *d_bloom is
+ * range-checked again against file_bytes: a d_bloom that was not written for
+ * this file never causes a read outside d_file[0, file_bytes). */
+typedef struct lv_sst_bloom {            /* device memory, 8-B aligned, always written */
+    uint64_t filter_offset, filter_size, array_offset, num, base_lg, present, why, reserved;
+} lv_sst_bloom;
+#define LV_SST_BLOOM_TABLE         1u
+#define LV_SST_BLOOM_EMPTY         2u
+#define LV_SST_BLOOM_BAD_METAINDEX 3u
+#define LV_SST_BLOOM_NO_ENTRY      4u
+#define LV_SST_BLOOM_BAD_HANDLE    5u
+#define LV_SST_BLOOM_BAD_TYPE      6u
+#define LV_SST_BLOOM_SHORT         7u
+#define LV_SST_BLOOM_BAD_ARRAY     8u
+#define LV_SST_GET_FILTERED 1u           /* lv_sst_get_result.reserved of a query the filter rejected */
+int lv_sst_bloom_open_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_table *d_table,
+                             lv_sst_bloom *d_bloom, uint32_t flags, void *stream);
+/* The host twin over file[0, table->file_bytes): 0, or LV_ERR_INVALID for a
+ * NULL table or bloom or a NULL file with table->file_bytes != 0. */
+int lv_sst_bloom_open_host(const uint8_t *file, const lv_sst_table *table, lv_sst_bloom *bloom);
+int lv_sst_get_bloom_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_table *d_table,
+                            const lv_sst_bloom *d_bloom,
+                            const uint8_t *d_qkeys, size_t qkeys_bytes, const uint64_t *d_q_off,
+                            const uint32_t *d_q_len, const uint64_t *d_q_seq, size_t nq,
+                            lv_sst_get_result *d_results, uint32_t flags, void *stream);
+/* One query on the host: lv_sst_get_host with the filter (bloom != NULL). */
+int lv_sst_get_bloom_host(const uint8_t *file, const lv_sst_table *table, const lv_sst_bloom *bloom,
+                          const uint8_t *qkey, size_t qkey_len, uint64_t seq, lv_sst_get_result *result);
 
 #ifdef __cplusplus
 }

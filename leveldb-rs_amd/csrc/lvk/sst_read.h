@@ -5,7 +5,9 @@
 // check program (tools/sst_get_host_check.cc) runs under a sanitizer is the
 // logic a lane runs.  Everything here reads file[0, file_bytes) only, whatever
 // the bytes say: every offset is a u64 compared against its limit before the
-// byte is touched, and no length is added to a pointer unchecked.
+// byte is touched, and no length is added to a pointer unchecked.  The filter
+// block's reader ("Bloom filter blocks": hash, bloom_open, may_match) is here
+// too, and get() asks it when given one; the build's filter emit uses hash.
 //
 // Keys are never materialised.  While a restart run is scanned the cursor
 // keeps, of the current internal key (prefix-compressed against its
@@ -210,10 +212,123 @@ LVR_FN Seek block_seek(const uint8_t *raw, uint64_t size, const Target &t, Curso
     }
 }
 
+// ---- the filter block (table.h, "Bloom filter blocks") ----
+
+constexpr uint32_t kBloomSeed = LV_SST_BLOOM_SEED;  // BloomHash(key) = Hash(key, this)
+
+// util/hash.rs (upstream's Hash) for one key at any alignment: the 4-byte
+// steps are assembled from bytes.
+LVR_FN uint32_t hash(const uint8_t *d, uint64_t n, uint32_t seed) {
+    constexpr uint32_t m = 0xc6a4a793u;
+    uint32_t h = seed ^ (m * static_cast<uint32_t>(n));
+    uint64_t i = 0;
+    for (; i + 4 <= n; i += 4) {
+        h += le32(d + i);
+        h *= m;
+        h ^= h >> 16;
+    }
+    const uint64_t rest = n - i;
+    if (rest >= 3) h += static_cast<uint32_t>(d[i + 2]) << 16;
+    if (rest >= 2) h += static_cast<uint32_t>(d[i + 1]) << 8;
+    if (rest >= 1) {
+        h += d[i];
+        h *= m;
+        h ^= h >> 24;
+    }
+    return h;
+}
+
+// BloomFilterPolicy::KeyMayMatch for a key's hash over the filter f[0, len).
+LVR_FN bool bloom_may_match(const uint8_t *f, uint64_t len, uint32_t h) {
+    if (len < 2) return false;
+    const uint64_t bits = (len - 1) * 8;
+    const uint32_t k = f[len - 1];
+    if (k > 30) return true;  // reserved for other encodings
+    const uint32_t delta = (h >> 17) | (h << 15);
+    for (uint32_t j = 0; j < k; ++j) {
+        const uint64_t pos = h % bits;
+        if (!(f[pos / 8] & (1u << (pos % 8)))) return false;
+        h += delta;
+    }
+    return true;
+}
+
+// Table::ReadMeta + ReadFilter over file[0, fb) whose metaindex block is
+// {mo, ms}: every field of *b.  Any failure is "no filter", never an error.
+LVR_FN void bloom_open(const uint8_t *file, uint64_t fb, uint64_t mo, uint64_t ms, lv_sst_bloom *b) {
+    constexpr char name[] = LV_SST_BLOOM_NAME;
+    constexpr uint32_t kName = sizeof(name) - 1;
+    *b = lv_sst_bloom{};
+    b->why = LV_SST_BLOOM_BAD_METAINDEX;
+    Restarts r;
+    if (!in_range(mo, ms, fb) || file[mo + ms] != LV_SST_NO_COMPRESSION || !restarts(file + mo, ms, &r)) return;
+    const uint8_t *raw = file + mo;
+    // the first entry not less than the name, walking from offset 0; of each
+    // key only its first kName + 1 bytes are kept
+    uint8_t key[kName + 1];
+    uint64_t at = 0, klen = 0;
+    Entry e{};
+    bool hit = false;
+    while (r.n && at < r.arr) {
+        if (!decode(raw, at, r.arr, &e) || e.shared > klen) return;
+        for (uint64_t i = e.shared; i < kName + 1 && i < static_cast<uint64_t>(e.shared) + e.non_shared; ++i)
+            key[i] = raw[e.key_at + (i - e.shared)];
+        klen = static_cast<uint64_t>(e.shared) + e.non_shared;
+        const uint64_t m = klen < kName ? klen : kName;
+        int c = 0;
+        for (uint64_t i = 0; i < m && !c; ++i)
+            c = key[i] < static_cast<uint8_t>(name[i]) ? -1 : key[i] > static_cast<uint8_t>(name[i]) ? 1 : 0;
+        if (!c) c = klen < kName ? -1 : klen > kName ? 1 : 0;
+        if (c >= 0) {
+            hit = c == 0;
+            break;
+        }
+        at = e.end();
+    }
+    b->why = LV_SST_BLOOM_NO_ENTRY;
+    if (!hit) return;
+    uint64_t fo, fs;
+    b->why = LV_SST_BLOOM_BAD_HANDLE;
+    if (!handle(raw, e.value_at(), e.end(), &fo, &fs) || !in_range(fo, fs, fb)) return;
+    b->why = LV_SST_BLOOM_BAD_TYPE;
+    if (file[fo + fs] != LV_SST_NO_COMPRESSION) return;
+    b->why = LV_SST_BLOOM_SHORT;
+    if (fs < 5) return;
+    const uint64_t array = le32(file + fo + fs - 5);
+    b->why = LV_SST_BLOOM_BAD_ARRAY;
+    if (array > fs - 5) return;
+    b->filter_offset = fo;
+    b->filter_size = fs;
+    b->array_offset = array;
+    b->num = (fs - 5 - array) / 4;
+    b->base_lg = file[fo + fs - 1];
+    b->present = 1;
+    b->why = 0;
+}
+
+// FilterBlockReader::KeyMayMatch.  Every offset of *b is range-checked again
+// against fb: a *b that was not written for this file reads nothing outside
+// it (and then answers "may match", as no filter does).
+LVR_FN bool may_match(const uint8_t *file, uint64_t fb, const lv_sst_bloom &b, uint64_t block_offset,
+                      const uint8_t *key, uint32_t klen) {
+    const uint64_t fs = b.filter_size, array = b.array_offset;
+    if (b.present != 1 || !in_range(b.filter_offset, fs, fb) || fs < 5 || array > fs - 5 ||
+        b.num > (fs - 5 - array) / 4)
+        return true;
+    const uint8_t *data = file + b.filter_offset;
+    const uint64_t i = b.base_lg < 64 ? block_offset >> b.base_lg : 0;
+    if (i >= b.num) return true;  // errors are potential matches
+    const uint64_t start = le32(data + array + 4 * i), limit = le32(data + array + 4 * i + 4);
+    if (start <= limit && limit <= array) return bloom_may_match(data + start, limit - start, hash(key, klen, kBloomSeed));
+    return start != limit;
+}
+
 // Table::InternalGet + SaveValue for one target over file[0, fb) whose index
-// block is {io, is}.  *res arrives zeroed; the status is returned.
+// block is {io, is}.  *res arrives zeroed; the status is returned.  With a
+// filter (bloom != nullptr) it is asked once the data block's handle is known
+// to be in range and before anything of the block is read.
 LVR_FN uint32_t get(const uint8_t *file, uint64_t fb, uint64_t io, uint64_t is, const Target &t,
-                    lv_sst_get_result *res) {
+                    lv_sst_get_result *res, const lv_sst_bloom *bloom = nullptr) {
     if (!fb) return LV_SST_GET_ABSENT;  // the empty table
     if (!in_range(io, is, fb)) return LV_SST_GET_CORRUPT;
     const uint8_t *idx = file + io;
@@ -234,6 +349,10 @@ LVR_FN uint32_t get(const uint8_t *file, uint64_t fb, uint64_t io, uint64_t is, 
     if (!probe(idx, r, lo, t, &c, &e)) return LV_SST_GET_CORRUPT;
     uint64_t off, size;
     if (!handle(idx, e.value_at(), e.end(), &off, &size) || !in_range(off, size, fb)) return LV_SST_GET_CORRUPT;
+    if (bloom && !may_match(file, fb, *bloom, off, t.q, t.ql)) {
+        res->reserved = LV_SST_GET_FILTERED;
+        return LV_SST_GET_ABSENT;
+    }
     if (file[off + size] != LV_SST_NO_COMPRESSION) return LV_SST_GET_CORRUPT;
     const Seek s = block_seek(file + off, size, t, &c, &e);
     if (s == kSeekCorrupt) return LV_SST_GET_CORRUPT;

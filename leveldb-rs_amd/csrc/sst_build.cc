@@ -11,6 +11,7 @@
 
 #include "../../include/lvgpu/crc32c.h"
 #include "../../include/lvgpu/table.h"
+#include "lvk/sst_read.h"
 
 namespace {
 
@@ -112,6 +113,18 @@ struct Block {
         has_last = true;
         ++counter;
     }
+    // The only entry of a block whose key is a plain byte string, not an
+    // internal key (the metaindex block's): shared = 0.
+    void add_only(const uint8_t *key, uint64_t klen, const uint8_t *value, uint64_t vlen) {
+        uint64_t at = base;
+        at += out.varint(at, 0);
+        at += out.varint(at, klen);
+        at += out.varint(at, vlen);
+        out.bytes(at, key, klen);
+        out.bytes(at + klen, value, vlen);
+        buffer = at + klen + vlen - base;
+        ++counter;
+    }
     uint64_t finish() {  // the raw size
         uint64_t at = base + buffer;
         for (uint64_t r : restarts) {
@@ -145,11 +158,67 @@ Sep short_successor(const IKey &a) {
     return {i, true};
 }
 
+// BloomFilterPolicy::CreateFilter over n key hashes into dst[0, bytes + 1).
+uint32_t bloom_k(uint32_t bpk) {
+    const uint32_t k = bpk * 69 / 100;
+    return k < 1 ? 1 : k > 30 ? 30 : k;
+}
+uint64_t bloom_bytes(uint64_t n, uint32_t bpk) {  // without the k byte
+    const unsigned __int128 want = static_cast<unsigned __int128>(n) * bpk;
+    const unsigned __int128 bits = want < 64 ? 64 : want;
+    const unsigned __int128 bytes = (bits + 7) / 8;
+    return bytes > (1ull << 62) ? 1ull << 62 : static_cast<uint64_t>(bytes);  // (no table comes near)
+}
+void bloom_fill(uint8_t *dst, uint64_t bytes, uint32_t bpk, const uint32_t *hashes, uint64_t n) {
+    const uint64_t bits = bytes * 8;
+    const uint32_t k = bloom_k(bpk);
+    std::memset(dst, 0, bytes);
+    dst[bytes] = static_cast<uint8_t>(k);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t h = hashes[i];
+        const uint32_t delta = (h >> 17) | (h << 15);
+        for (uint32_t j = 0; j < k; ++j) {
+            const uint64_t pos = h % bits;
+            dst[pos / 8] |= static_cast<uint8_t>(1u << (pos % 8));
+            h += delta;
+        }
+    }
+}
+
+// FilterBlockBuilder (base lg 11), keys held as their Bloom hashes.
+struct FilterBlock {
+    uint32_t bpk;
+    std::vector<uint32_t> pending;
+    std::vector<uint8_t> result;
+    std::vector<uint64_t> offsets;
+    uint64_t keys = 0;
+    void add(const uint8_t *k, uint64_t n) {
+        pending.push_back(lvr::hash(k, n, lvr::kBloomSeed));
+        ++keys;
+    }
+    void generate() {
+        offsets.push_back(result.size());
+        if (pending.empty()) return;
+        const uint64_t bytes = bloom_bytes(pending.size(), bpk), at = result.size();
+        result.resize(at + bytes + 1);
+        bloom_fill(result.data() + at, bytes, bpk, pending.data(), pending.size());
+        pending.clear();
+    }
+    void start_block(uint64_t offset) {
+        while ((offset >> LV_SST_FILTER_BASE_LG) > offsets.size()) generate();
+    }
+    uint64_t finish_size() {  // the block's size; the array follows the filters
+        if (!pending.empty()) generate();
+        return result.size() + 4 * offsets.size() + 5;
+    }
+};
+
 struct Run {
     const uint8_t *payload;
     const lv_wb_op *ops;
     const uint32_t *order;
     uint64_t n, block_size, interval;
+    uint32_t bpk;  // 0: no filter policy
 };
 
 IKey ikey(const Run &R, uint64_t i) {
@@ -163,8 +232,10 @@ IKey ikey(const Run &R, uint64_t i) {
 
 // One walk.  index_at: where the index block goes (the write pass knows it
 // from the sizing pass).  handles is NULL in a sizing pass; a write pass runs
-// only with data_blocks <= block_cap, so it has room for data_blocks + 2 pairs.
-void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, lv_sst_build_totals *t) {
+// only with data_blocks <= block_cap, so it has room for data_blocks + 2 pairs
+// (+ 3 with a filter policy: the filter block's comes before the metaindex's).
+void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, lv_sst_build_totals *t,
+          lv_sst_bloom_totals *bt) {
     uint64_t offset = 0, blocks = 0;
     bool large = false;
     Block index(out, index_at, 1);
@@ -172,6 +243,7 @@ void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, l
     bool pending = false;
     uint64_t pend_off = 0, pend_size = 0;
     IKey last{};
+    FilterBlock filter{R.bpk};
     auto add_index = [&](const Sep &s) {
         IKey k;
         k.k = last.k;
@@ -201,6 +273,7 @@ void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, l
         pend_off = offset;
         pend_size = size;
         offset += size + LV_SST_TRAILER_SIZE;
+        if (R.bpk) filter.start_block(offset);
     };
     if (R.n) {
         std::optional<Block> data;
@@ -210,6 +283,7 @@ void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, l
             const IKey key = ikey(R, i);
             if (pending) add_index(shortest_separator(last, key));
             last = key;
+            if (R.bpk) filter.add(key.k, key.ulen);
             data->add(key, R.payload + o.val_off, o.val_len);
             if (data->estimate() >= R.block_size) {
                 write_block(*data);
@@ -226,15 +300,49 @@ void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, l
     }
     t->data_blocks = blocks;
     if (!R.n) return;  // no file
-    // the metaindex block: an empty BlockBuilder
+    uint64_t nh = blocks;  // the next handle pair
+    uint8_t fh[LV_SST_BLOCK_HANDLE_MAX];
+    size_t fhn = 0;
+    if (R.bpk) {  // the filter block: the filters, their offsets, array_offset, the base
+        const uint64_t size = filter.finish_size(), array = filter.result.size();
+        if (size >= kLargeBlock) large = true;
+        if (out.file) {
+            out.bytes(offset, filter.result.data(), array);
+            uint64_t at = offset + array;
+            for (uint64_t o : filter.offsets) {
+                out.fixed32(at, o);
+                at += 4;
+            }
+            out.fixed32(at, array);
+            out.file[at + 4] = LV_SST_FILTER_BASE_LG;
+        }
+        out.trailer(offset, size);
+        if (handles) {
+            handles[2 * nh] = offset;
+            handles[2 * nh + 1] = size;
+        }
+        ++nh;
+        bt->filter_offset = offset;
+        bt->filter_size = size;
+        bt->filters = filter.offsets.size();
+        bt->filter_keys = filter.keys;
+        fhn = lv_sst_block_handle_encode(offset, size, fh);
+        offset += size + LV_SST_TRAILER_SIZE;
+    }
+    // the metaindex block: an empty BlockBuilder, or one with the filter's entry
     Block meta(out, offset, R.interval);
+    if (R.bpk) {
+        static const uint8_t name[] = LV_SST_BLOOM_NAME;
+        meta.add_only(name, sizeof(name) - 1, fh, fhn);
+    }
     t->metaindex_offset = offset;
     t->metaindex_size = meta.finish();
     out.trailer(offset, t->metaindex_size);
     if (handles) {
-        handles[2 * blocks] = offset;
-        handles[2 * blocks + 1] = t->metaindex_size;
+        handles[2 * nh] = offset;
+        handles[2 * nh + 1] = t->metaindex_size;
     }
+    ++nh;
     offset += t->metaindex_size + LV_SST_TRAILER_SIZE;
     if (pending) add_index(short_successor(last));
     t->index_offset = offset;
@@ -242,8 +350,8 @@ void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, l
     if (t->index_size >= kLargeBlock) large = true;
     out.trailer(offset, t->index_size);
     if (handles) {
-        handles[2 * blocks + 2] = offset;
-        handles[2 * blocks + 3] = t->index_size;
+        handles[2 * nh] = offset;
+        handles[2 * nh + 1] = t->index_size;
     }
     offset += t->index_size + LV_SST_TRAILER_SIZE;
     if (out.file)
@@ -272,10 +380,18 @@ uint64_t lv_sst_build_file_bound(uint64_t payload_bytes, uint64_t op_cap, const 
     return b > ~0ull ? ~0ull : static_cast<uint64_t>(b);
 }
 
-int lv_sst_build_host(const uint8_t *payload, size_t payload_bytes, const lv_wb_op *ops, const uint32_t *order,
-                      const lv_mt_totals *mt_totals, const lv_sst_build_options *opt, uint8_t *file, uint64_t file_cap,
-                      uint64_t *handles, size_t block_cap, lv_sst_build_totals *totals) {
+}  // extern "C"
+
+namespace {
+
+// lv_sst_build_host (bpk == 0, bloom_totals == NULL) and lv_sst_build_bloom_host.
+int build_host(const uint8_t *payload, size_t payload_bytes, const lv_wb_op *ops, const uint32_t *order,
+               const lv_mt_totals *mt_totals, const lv_sst_build_options *opt, uint32_t bpk, uint8_t *file,
+               uint64_t file_cap, uint64_t *handles, size_t block_cap, lv_sst_build_totals *totals,
+               lv_sst_bloom_totals *bloom_totals) {
     uint64_t bs, ri;
+    lv_sst_bloom_totals bt{}, unused{};
+    if (bloom_totals) *bloom_totals = bt;
     if (!totals || !mt_totals || !options_ok(opt, &bs, &ri)) return LV_ERR_INVALID;
     if ((!payload && payload_bytes) || (!file && file_cap) || (!handles && block_cap)) return LV_ERR_INVALID;
     const bool sizing = !file && !file_cap;
@@ -296,15 +412,62 @@ int lv_sst_build_host(const uint8_t *payload, size_t payload_bytes, const lv_wb_
         return 0;
     }
     t.entries = n;
-    const Run R{payload, ops, order, n, bs, ri};
-    walk(R, Sink{nullptr}, 0, nullptr, &t);
+    const Run R{payload, ops, order, n, bs, ri, bpk};
+    walk(R, Sink{nullptr}, 0, nullptr, &t, &bt);
     if (t.data_blocks > block_cap && !(sizing && !handles)) t.status |= LV_SST_BUILD_HANDLE_OVER;
     if (t.file_bytes > file_cap && !sizing) t.status |= LV_SST_BUILD_FILE_OVER;
     if (!t.status && file && n) {
         lv_sst_build_totals again{};
-        walk(R, Sink{file}, t.index_offset, handles, &again);
+        walk(R, Sink{file}, t.index_offset, handles, &again, &unused);
     }
     *totals = t;
+    if (bloom_totals && !t.status) *bloom_totals = bt;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lv_sst_build_host(const uint8_t *payload, size_t payload_bytes, const lv_wb_op *ops, const uint32_t *order,
+                      const lv_mt_totals *mt_totals, const lv_sst_build_options *opt, uint8_t *file, uint64_t file_cap,
+                      uint64_t *handles, size_t block_cap, lv_sst_build_totals *totals) {
+    return build_host(payload, payload_bytes, ops, order, mt_totals, opt, 0, file, file_cap, handles, block_cap, totals,
+                      nullptr);
+}
+
+int lv_sst_build_bloom_host(const uint8_t *payload, size_t payload_bytes, const lv_wb_op *ops, const uint32_t *order,
+                            const lv_mt_totals *mt_totals, const lv_sst_build_options *opt,
+                            const lv_sst_bloom_options *bloom, uint8_t *file, uint64_t file_cap, uint64_t *handles,
+                            size_t block_cap, lv_sst_build_totals *totals, lv_sst_bloom_totals *bloom_totals) {
+    if (!bloom || !bloom_totals || bloom->bits_per_key < 1 || bloom->bits_per_key > 64 || bloom->reserved)
+        return LV_ERR_INVALID;
+    return build_host(payload, payload_bytes, ops, order, mt_totals, opt, bloom->bits_per_key, file, file_cap, handles,
+                      block_cap, totals, bloom_totals);
+}
+
+uint64_t lv_sst_build_bloom_file_bound(uint64_t payload_bytes, uint64_t op_cap, const lv_sst_build_options *opt,
+                                       const lv_sst_bloom_options *bloom) {
+    (void)opt;
+    if (!op_cap || !bloom || bloom->bits_per_key < 1 || bloom->bits_per_key > 64 || bloom->reserved) return 0;
+    const unsigned __int128 n = op_cap, p = payload_bytes;
+    const unsigned __int128 b = p * 2 + n * 75 + 70 + n * bloom->bits_per_key / 8 + n * 9 + (p + n * 36) / 512 + 72;
+    return b > ~0ull ? ~0ull : static_cast<uint64_t>(b);
+}
+
+size_t lv_bloom_filter_bytes(size_t n, uint32_t bits_per_key) {
+    return bits_per_key ? static_cast<size_t>(bloom_bytes(n, bits_per_key) + 1) : 0;
+}
+
+int lv_bloom_create_filter(const uint8_t *keys, const uint64_t *off, const uint32_t *len, size_t n,
+                           uint32_t bits_per_key, uint8_t *dst) {
+    if (!dst || !bits_per_key || (n && (!off || !len))) return LV_ERR_INVALID;
+    std::vector<uint32_t> hashes(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (!keys && len[i]) return LV_ERR_INVALID;
+        hashes[i] = lvr::hash(keys ? keys + off[i] : nullptr, len[i], lvr::kBloomSeed);
+    }
+    bloom_fill(dst, bloom_bytes(n, bits_per_key), bits_per_key, hashes.data(), n);
     return 0;
 }
 

@@ -1,6 +1,8 @@
 // lv_sst_build_device: the sorted memtable of lv_memtable_build_device written
 // as a complete SSTable image in HBM (include/lvgpu/table.h spells the format
-// out; csrc/sst_build.cc is the serial twin).
+// out; csrc/sst_build.cc is the serial twin).  lv_sst_build_bloom_device is
+// the same call with a filter policy: the same kernels with SbArgs::bpk != 0,
+// and the four sb_bloom_* kernels listed below.
 //
 // Block boundaries are a serial chain: where block b ends decides which
 // entries of block b + 1 are restarts, and so their sizes.  The chain is cut
@@ -44,6 +46,20 @@
 //              a time) in 16-byte granules of the destination's alignment.
 //   sb_tail    d_handles and the padding of the workspace copy, the
 //              metaindex block, the index's count, the footer.
+//   with a filter policy (table.h, "Bloom filter blocks"), by block id:
+//   sb_bloom_sizes    (before the plan) per data block whether it is the first
+//              of its 2 KiB window of file offsets, the window's key count
+//              (the entries up to the first block of a later window) and its
+//              filter's size -> tile scan, and sb_carry once more.
+//   sb_bloom_emit     (behind sb_emit) a wave per filter: bits zeroed in LDS,
+//              the lanes hash the window's user keys and OR the k bits in
+//              with LDS atomics, plain stores of the destination's alignment.
+//              A filter beyond kSbBloomLds bytes is stored as zeros.
+//   sb_bloom_big      the bits of those, by atomic OR on aligned dwords of
+//              d_file; the launch stores nothing else.
+//   sb_bloom_offsets  a lane per window: its filter's start offset.
+//   sb_tail then also writes array_offset, the base byte and the metaindex
+//   entry; the filter block joins the index block in the CRC batch.
 //   the seal   sst_blocks_kernel<seal> (sst.hip) over the workspace handles of
 //              the data blocks and the metaindex block, padded to
 //              block_cap + 2 with {2^64 - 1, 0}, which it skips.  The index
@@ -61,6 +77,7 @@
 // with this file's tile, thread count and copy knobs.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 
 #include "../../include/lvgpu/crc32c.h"
@@ -68,6 +85,7 @@
 #include "lv_internal.h"
 #include "lvh.h"
 #include "lvk/knobs.h"
+#include "lvk/sst_read.h"
 #include "lvk/stage.h"
 
 namespace lvk {
@@ -79,6 +97,9 @@ constexpr uint32_t kSbThreads = 256;
 constexpr uint32_t kSbPer = kSbTile / kSbThreads;
 constexpr uint32_t kSbMaxR = LV_SST_MAX_RESTART_INTERVAL;
 constexpr uint64_t kSbLarge = 0xffffffffull;  // raw sizes from here on: sst_in_range refuses them
+constexpr uint32_t kSbBloomLds = 2048;        // bytes of filter bits a wave holds in LDS (1,638 keys at 10 bits per key)
+constexpr uint32_t kSbBloomName = sizeof(LV_SST_BLOOM_NAME) - 1;
+static_assert(kSbBloomName == 34 && kSbBloomLds % 4 == 0, "the metaindex key; whole LDS words");
 static_assert(kSbTile % kSbThreads == 0 && kSbTile >= kSbMaxR, "a tile holds every residue of a restart interval");
 static_assert(kSbTile * 16 <= 65536, "two u64 scan arrays fit the LDS a workgroup may declare");
 static_assert(kSbWaveCopy >= 16, "a wave copy has at least one granule");
@@ -87,6 +108,12 @@ static_assert(kSbCopyLanes >= 16 && 64 % kSbCopyLanes == 0, "a copy's lanes cove
 struct SbHead {  // workspace, zeroed by sb_init
     uint32_t bad, large, go, pad;
     unsigned long long nblocks, data_bytes, idx_bytes, meta_off, index_off, index_size;
+};
+
+struct SbBloomHead {  // workspace, zeroed by sb_init
+    unsigned long long filt_bytes, filter_off, filter_size, filters, meta_size;
+    unsigned long long big;  // some filter is beyond kSbBloomLds bytes: sb_bloom_big has work
+    unsigned long long pad[2];
 };
 
 struct SbArgs {
@@ -116,6 +143,19 @@ struct SbArgs {
     uint64_t *idx_off;       // [1] the index block as a one-buffer batch of the offsets API:
     uint32_t *idx_len;       // [1] contents || type
     uint32_t *idx_crc;       // [1] its masked crc
+    // lv_sst_build_bloom_device (bpk != 0; table.h, "Bloom filter blocks").  The
+    // arrays are by block id and hold op_cap entries: a table has no more
+    // blocks than entries, whatever block_cap is.  With a filter the batch
+    // above has two buffers, the index block and the filter block, and wsh
+    // 2 (block_cap + 3) words.
+    uint32_t bpk;
+    lv_sst_bloom_totals *btotals;
+    SbBloomHead *bh;
+    uint64_t *boff;          // [cap] the block's file offset
+    uint32_t *bstart;        // [cap] its first entry
+    uint32_t *Fn;            // [cap] the keys of the window it is the first block of, or 0
+    uint64_t *Fl;            // [cap] tile-local exclusive scan of the filters' bytes
+    uint64_t *cF;            // [tiles]
 };
 
 // The entries, or 0 when there is no table to read.
@@ -201,6 +241,7 @@ __device__ __forceinline__ uint64_t sb_estimate(const SbArgs &A, uint64_t s, uin
 __global__ void sb_init(const SbArgs A) {
     SbHead h{};
     *A.head = h;
+    if (A.bpk) *A.bh = SbBloomHead{};
 }
 
 // Kernel 1: sizes and the tile-local scans of P and S.
@@ -264,13 +305,14 @@ __global__ __launch_bounds__(kSbThreads) void sb_sizes(const SbArgs A) {
 // Kernel 2: the exclusive scan over the tiles of column c, in place; one wave
 // per column.  Column c is col[c + t * stride], t < tiles; its sum goes to
 // total[c] when total is not null.  which: 0 = {P, S residues} (cP is column
-// R), 1 = {block count, file bytes}, 2 = {index bytes}.
+// R), 1 = {block count, file bytes}, 2 = {index bytes}, 3 = {filter bytes}.
 __global__ __launch_bounds__(kSbThreads) void sb_carry(const SbArgs A, uint32_t which) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t c = blockIdx.x * (kSbThreads / 64) + (threadIdx.x >> 6);
     const uint64_t n = sb_entries(A);
     if (!n || A.head->bad) return;
-    const uint64_t tiles = (n + kSbTile - 1) / kSbTile;
+    // (the filters' column is by block id)
+    const uint64_t tiles = ((which == 3 ? static_cast<uint64_t>(A.head->nblocks) : n) + kSbTile - 1) / kSbTile;
     uint64_t *col;
     uint64_t stride = 1;
     unsigned long long *total = nullptr;
@@ -282,10 +324,14 @@ __global__ __launch_bounds__(kSbThreads) void sb_carry(const SbArgs A, uint32_t 
         if (c > 1) return;
         col = c ? A.cB : A.cC;
         total = c ? &A.head->data_bytes : &A.head->nblocks;
-    } else {
+    } else if (which == 2) {
         if (c > 0) return;
         col = A.cI;
         total = &A.head->idx_bytes;
+    } else {
+        if (c > 0) return;
+        col = A.cF;
+        total = &A.bh->filt_bytes;
     }
     const uint64_t run = carry_scan(col, stride, tiles, lane);
     if (total && lane == 0) *total = run;
@@ -426,6 +472,10 @@ __global__ __launch_bounds__(kSbThreads) void sb_index(const SbArgs A) {
                 A.wsh[2 * b] = off;
                 A.wsh[2 * b + 1] = raw;
             }
+            if (A.bpk) {
+                A.boff[b] = off;
+                A.bstart[b] = static_cast<uint32_t>(s);
+            }
             v = sb_index_entry(A, e, n, load_op(A.ops + A.order[e]), off, raw).size;
         }
         s_i[j] = v;
@@ -445,6 +495,7 @@ __global__ __launch_bounds__(kSbThreads) void sb_index(const SbArgs A) {
 __global__ void sb_plan(const SbArgs A) {
     SbHead *h = A.head;
     lv_sst_build_totals t{};
+    lv_sst_bloom_totals bt{};
     uint64_t n = A.mt->entries;
     if (A.mt->status || n > A.op_cap || h->bad) {
         t.status = LV_SST_BUILD_NO_TABLE;
@@ -456,7 +507,17 @@ __global__ void sb_plan(const SbArgs A) {
         t.data_blocks = nb;
         t.metaindex_offset = h->data_bytes;
         t.metaindex_size = 8;
-        t.index_offset = t.metaindex_offset + 8 + LV_SST_TRAILER_SIZE;
+        if (A.bpk) {  // the filter block goes first; the metaindex block holds its entry
+            const uint64_t last = A.boff[nb - 1] >> LV_SST_FILTER_BASE_LG, ends = h->data_bytes >> LV_SST_FILTER_BASE_LG;
+            bt.filters = last + 1 > ends ? last + 1 : ends;
+            bt.filter_offset = h->data_bytes;
+            bt.filter_size = A.bh->filt_bytes + 4 * bt.filters + 5;
+            bt.filter_keys = n;
+            if (bt.filter_size >= kSbLarge) t.status |= LV_SST_BUILD_BLOCK_LARGE;
+            t.metaindex_offset = bt.filter_offset + bt.filter_size + LV_SST_TRAILER_SIZE;
+            t.metaindex_size = 3 + kSbBloomName + sb_varint_len(bt.filter_offset) + sb_varint_len(bt.filter_size) + 8;
+        }
+        t.index_offset = t.metaindex_offset + t.metaindex_size + LV_SST_TRAILER_SIZE;
         t.index_size = h->idx_bytes + 4 * nb + 4;
         t.file_bytes = t.index_offset + t.index_size + LV_SST_TRAILER_SIZE + LV_SST_FOOTER_SIZE;
         if (h->large || t.index_size >= kSbLarge) t.status |= LV_SST_BUILD_BLOCK_LARGE;
@@ -467,13 +528,21 @@ __global__ void sb_plan(const SbArgs A) {
             h->meta_off = t.metaindex_offset;
             h->index_off = t.index_offset;
             h->index_size = t.index_size;
-            A.wsh[2 * nb] = t.metaindex_offset;
-            A.wsh[2 * nb + 1] = t.metaindex_size;
-            A.wsh[2 * nb + 2] = t.index_offset;
-            A.wsh[2 * nb + 3] = t.index_size;
+            uint64_t *w = A.wsh + 2 * nb;
+            if (A.bpk) {
+                A.bh->filter_off = *w++ = bt.filter_offset;
+                A.bh->filter_size = *w++ = bt.filter_size;
+                A.bh->filters = bt.filters;
+                A.bh->meta_size = t.metaindex_size;
+            }
+            *w++ = t.metaindex_offset;
+            *w++ = t.metaindex_size;
+            *w++ = t.index_offset;
+            *w++ = t.index_size;
         }
     }
     *A.totals = t;
+    if (A.bpk) *A.btotals = t.status || !n ? lv_sst_bloom_totals{} : bt;
 }
 
 // Kernel 8: the entries, the restart arrays, the index entries.  Every lane of
@@ -557,13 +626,16 @@ __global__ __launch_bounds__(kSbThreads) void sb_tail(const SbArgs A) {
     const SbHead *h = A.head;
     const uint64_t j = static_cast<uint64_t>(blockIdx.x) * kSbThreads + threadIdx.x;
     const bool go = h->go;
-    const uint64_t nh = go ? h->nblocks + 2 : 0;
-    if (j < A.block_cap + 2) {
+    const uint64_t extra = A.bpk ? 3 : 2;  // the pairs behind the data blocks'
+    const uint64_t nh = go ? h->nblocks + extra : 0;
+    if (j < A.block_cap + extra) {
         if (j < nh) {
             A.handles[2 * j] = A.wsh[2 * j];
             A.handles[2 * j + 1] = A.wsh[2 * j + 1];
         }
-        if (j + 1 >= nh) {  // the seal skips a handle out of range without touching the file
+        // the seal's are the data blocks and the metaindex block (the last pair
+        // but one); it skips a handle out of range without touching the file
+        if (!(go && (j < h->nblocks || j + 2 == nh))) {
             A.wsh[2 * j] = ~0ull;
             A.wsh[2 * j + 1] = 0;
         }
@@ -571,16 +643,38 @@ __global__ __launch_bounds__(kSbThreads) void sb_tail(const SbArgs A) {
     if (j == 0) {
         A.idx_off[0] = go ? h->index_off : 0;
         A.idx_len[0] = go ? static_cast<uint32_t>(h->index_size + 1) : 0;  // (< 2^32 - 1: the plan checked)
+        if (A.bpk) {
+            A.idx_off[1] = go ? A.bh->filter_off : 0;
+            A.idx_len[1] = go ? static_cast<uint32_t>(A.bh->filter_size + 1) : 0;
+        }
     }
     if (j == 0 && go) {
         A.file[h->index_off + h->index_size] = LV_SST_NO_COMPRESSION;
-        uint8_t *m = A.file + h->meta_off;  // an empty BlockBuilder: 00 00 00 00 01 00 00 00
-        sb_put_fixed32(m, 0);
+        uint8_t *m = A.file + h->meta_off;
+        uint64_t meta_size = 8;
+        if (A.bpk) {
+            const SbBloomHead *bh = A.bh;
+            // the filter block's end: array_offset, the base, the type byte
+            uint8_t *e = A.file + bh->filter_off + bh->filter_size;
+            sb_put_fixed32(e - 5, static_cast<uint32_t>(bh->filt_bytes));
+            e[-1] = LV_SST_FILTER_BASE_LG;
+            e[0] = LV_SST_NO_COMPRESSION;
+            // the metaindex block's one entry: shared 0, the name, the filter block's handle
+            constexpr char name[] = LV_SST_BLOOM_NAME;
+            meta_size = bh->meta_size;
+            m = sb_put_varint(m, 0);
+            m = sb_put_varint(m, kSbBloomName);
+            m = sb_put_varint(m, meta_size - 3 - kSbBloomName - 8);
+            for (uint32_t t = 0; t < kSbBloomName; ++t) *m++ = static_cast<uint8_t>(name[t]);
+            m = sb_put_varint(m, bh->filter_off);
+            m = sb_put_varint(m, bh->filter_size);
+        }
+        sb_put_fixed32(m, 0);  // (an empty BlockBuilder: 00 00 00 00 01 00 00 00)
         sb_put_fixed32(m + 4, 1);
         sb_put_fixed32(A.file + h->index_off + h->idx_bytes + 4 * h->nblocks, static_cast<uint32_t>(h->nblocks));
         uint8_t *f = A.file + h->index_off + h->index_size + LV_SST_TRAILER_SIZE, *q = f;
         q = sb_put_varint(q, h->meta_off);
-        q = sb_put_varint(q, 8);
+        q = sb_put_varint(q, meta_size);
         q = sb_put_varint(q, h->index_off);
         q = sb_put_varint(q, h->index_size);
         while (q < f + 40) *q++ = 0;
@@ -591,7 +685,195 @@ __global__ __launch_bounds__(kSbThreads) void sb_tail(const SbArgs A) {
 // Kernel 10 (one thread): the index block's trailer from the batch's masked crc.
 __global__ void sb_index_trailer(const SbArgs A) {
     const SbHead *h = A.head;
-    if (h->go) sb_put_fixed32(A.file + h->index_off + h->index_size + 1, A.idx_crc[0]);
+    if (!h->go) return;
+    sb_put_fixed32(A.file + h->index_off + h->index_size + 1, A.idx_crc[0]);
+    if (A.bpk) sb_put_fixed32(A.file + A.bh->filter_off + A.bh->filter_size + 1, A.idx_crc[1]);
+}
+
+// ---- the filter block (lv_sst_build_bloom_device) ----
+
+// Bytes of the Bloom filter over `keys` keys, without its k byte.
+__device__ __forceinline__ uint64_t sb_bloom_bytes(uint64_t keys, uint32_t bpk) {
+    const uint64_t want = keys * bpk;  // keys < 2^32, bpk <= 64
+    return ((want < 64 ? 64 : want) + 7) / 8;
+}
+__device__ __forceinline__ uint32_t sb_bloom_k(uint32_t bpk) {
+    const uint32_t k = bpk * 69 / 100;
+    return k < 1 ? 1 : k > 30 ? 30 : k;
+}
+
+// Kernel B1, a lane per data block (by id, after sb_index and the layout's
+// carry): whether it is the first block of its window, then the keys of the
+// window (the entries up to the first block of a later window, found by a
+// bounded binary search over the block offsets) and its filter's size; the
+// tile scan of the sizes.
+__global__ __launch_bounds__(kSbThreads) void sb_bloom_sizes(const SbArgs A) {
+    __shared__ uint64_t s_f[kSbTile];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n = sb_entries(A);
+    if (!n || A.head->bad) return;
+    const uint64_t nb = A.head->nblocks;
+    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kSbTile;
+    if (base >= nb) return;
+    const uint32_t cnt = static_cast<uint32_t>(nb - base < kSbTile ? nb - base : kSbTile);
+    uint64_t own[kSbPer];
+#pragma unroll
+    for (uint32_t k = 0; k < kSbPer; ++k) {
+        const uint32_t j = tid + k * kSbThreads;
+        uint64_t v = 0;
+        if (j < cnt) {
+            const uint64_t b = base + j, w = A.boff[b] >> LV_SST_FILTER_BASE_LG;
+            uint32_t keys = 0;
+            if (b == 0 || (A.boff[b - 1] >> LV_SST_FILTER_BASE_LG) != w) {
+                const uint64_t lim = (w + 1) << LV_SST_FILTER_BASE_LG;
+                uint64_t lo = b + 1, hi = nb;
+                for (uint32_t it = 0; it < 40 && lo < hi; ++it) {
+                    const uint64_t mid = lo + (hi - lo) / 2;
+                    if (A.boff[mid] >= lim)
+                        hi = mid;
+                    else
+                        lo = mid + 1;
+                }
+                keys = static_cast<uint32_t>((lo < nb ? A.bstart[lo] : n) - A.bstart[b]);
+                v = sb_bloom_bytes(keys, A.bpk) + 1;
+                if (v - 1 > kSbBloomLds) atomicOr(&A.bh->big, 1ull);
+            }
+            A.Fn[b] = keys;
+        }
+        own[k] = v;
+        s_f[j] = v;
+    }
+    __syncthreads();
+    tile_scan<kSbTile, kSbThreads>(s_f, 1, tid);
+#pragma unroll
+    for (uint32_t k = 0; k < kSbPer; ++k) {
+        const uint32_t j = tid + k * kSbThreads;
+        if (j < cnt) A.Fl[base + j] = s_f[j] - own[k];
+    }
+    if (tid == 0) A.cF[blockIdx.x] = s_f[cnt - 1];
+}
+
+// total bytes at dst from the LDS bytes at src: dst's ragged head and tail
+// byte by byte, between them dwords of dst's alignment.  One wave.
+__device__ __forceinline__ void sb_bloom_store(uint8_t *dst, const uint8_t *src, uint32_t total, uint32_t lane) {
+    uint32_t head = static_cast<uint32_t>((4u - (reinterpret_cast<uintptr_t>(dst) & 3u)) & 3u);
+    if (head > total) head = total;
+    const uint32_t words = (total - head) / 4, tail = (total - head) % 4;
+    if (lane < head) dst[lane] = src[lane];
+    for (uint32_t g = lane; g < words; g += 64) {
+        const uint8_t *p = src + head + 4 * g;
+        *reinterpret_cast<uint32_t *>(dst + head + 4 * g) = lvr::le32(p);
+    }
+    if (lane < tail) dst[head + 4 * words + lane] = src[head + 4 * words + lane];
+}
+
+// Kernel B2, the filter emit: a wave per first-of-its-window block in a
+// grid-stride loop over the data blocks.  The filter's bits are zeroed in the
+// wave's LDS, each lane hashes user keys of the window and ORs their k bits in
+// with LDS atomics (order-free: the bytes do not depend on the schedule), and
+// the wave stores the bytes and the k byte.  A filter beyond kSbBloomLds bytes
+// is stored as zeros here; sb_bloom_big sets its bits.
+__global__ __launch_bounds__(kSbThreads) void sb_bloom_emit(const SbArgs A) {
+    __shared__ uint32_t s_bits[kSbThreads / 64][kSbBloomLds / 4 + 1];
+    if (!A.head->go) return;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t nb = A.head->nblocks, step = static_cast<uint64_t>(gridDim.x) * (kSbThreads / 64);
+    const uint32_t k = sb_bloom_k(A.bpk);
+    uint32_t *bits = s_bits[wave];
+    uint8_t *fbase = A.file + A.bh->filter_off;
+    for (uint64_t b = static_cast<uint64_t>(blockIdx.x) * (kSbThreads / 64) + wave; b < nb; b += step) {  // wave-uniform
+        const uint32_t keys = A.Fn[b];
+        if (!keys) continue;
+        const uint64_t bytes = sb_bloom_bytes(keys, A.bpk);
+        uint8_t *dst = fbase + A.Fl[b] + A.cF[b / kSbTile];
+        if (bytes > kSbBloomLds) {
+            const uint64_t head = (4u - (reinterpret_cast<uintptr_t>(dst) & 3u)) & 3u;  // < 8 <= bytes
+            const uint64_t words = (bytes - head) / 4, tail = (bytes - head) % 4;
+            if (lane < head) dst[lane] = 0;
+            for (uint64_t g = lane; g < words; g += 64) *reinterpret_cast<uint32_t *>(dst + head + 4 * g) = 0;
+            if (lane < tail) dst[head + 4 * words + lane] = 0;
+            if (lane == 0) dst[bytes] = static_cast<uint8_t>(k);
+            continue;
+        }
+        const uint32_t nbytes = static_cast<uint32_t>(bytes), nbits = nbytes * 8;
+        for (uint32_t w = lane; w <= nbytes / 4; w += 64) bits[w] = 0;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (lane == 0) atomicOr(&bits[nbytes / 4], k << (8 * (nbytes % 4)));  // the k byte
+        const uint64_t s = A.bstart[b];
+        for (uint32_t i = lane; i < keys; i += 64) {
+            const lv_wb_op o = load_op(A.ops + A.order[s + i]);
+            uint32_t h = lvr::hash(A.payload + o.key_off, o.key_len, lvr::kBloomSeed);
+            const uint32_t delta = (h >> 17) | (h << 15);
+            for (uint32_t j = 0; j < k; ++j) {
+                const uint32_t pos = h % nbits;
+                atomicOr(&bits[pos >> 5], 1u << (pos & 31u));  // little-endian: byte pos / 8, bit pos % 8
+                h += delta;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        sb_bloom_store(dst, reinterpret_cast<const uint8_t *>(bits), nbytes + 1, lane);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();  // the stores' LDS reads precede the next filter's zeroing
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
+// Kernel B3: the bits of the filters sb_bloom_emit zero-filled, set with
+// atomic ORs on aligned dwords of d_file.  This launch stores nothing else, so
+// a dword such a filter shares with its neighbours keeps their bytes.
+__global__ __launch_bounds__(kSbThreads) void sb_bloom_big(const SbArgs A) {
+    if (!A.head->go || !A.bh->big) return;  // (sb_bloom_sizes found none: the usual case)
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t nb = A.head->nblocks, step = static_cast<uint64_t>(gridDim.x) * (kSbThreads / 64);
+    const uint32_t k = sb_bloom_k(A.bpk);
+    uint8_t *fbase = A.file + A.bh->filter_off;
+    for (uint64_t b = static_cast<uint64_t>(blockIdx.x) * (kSbThreads / 64) + wave; b < nb; b += step) {
+        const uint32_t keys = A.Fn[b];
+        if (!keys) continue;
+        const uint64_t bytes = sb_bloom_bytes(keys, A.bpk), nbits = bytes * 8;
+        if (bytes <= kSbBloomLds) continue;
+        const uintptr_t dst = reinterpret_cast<uintptr_t>(fbase + A.Fl[b] + A.cF[b / kSbTile]);
+        const uint64_t s = A.bstart[b];
+        for (uint32_t i = lane; i < keys; i += 64) {
+            const lv_wb_op o = load_op(A.ops + A.order[s + i]);
+            uint32_t h = lvr::hash(A.payload + o.key_off, o.key_len, lvr::kBloomSeed);
+            const uint32_t delta = (h >> 17) | (h << 15);
+            for (uint32_t j = 0; j < k; ++j) {
+                const uint64_t pos = h % nbits;
+                const uintptr_t at = dst + pos / 8;
+                atomicOr(reinterpret_cast<uint32_t *>(at & ~static_cast<uintptr_t>(3)),
+                         1u << (8 * static_cast<uint32_t>(at & 3u) + static_cast<uint32_t>(pos % 8)));
+                h += delta;
+            }
+        }
+    }
+}
+
+// Kernel B4, a lane per window in a grid-stride loop: the filter's start
+// offset.  The first block at or beyond the window's first byte is the first
+// of its own window, whose filter starts where this window's does (an empty
+// window's filter is zero bytes); with no such block every filter lies before.
+__global__ __launch_bounds__(kSbThreads) void sb_bloom_offsets(const SbArgs A) {
+    if (!A.head->go) return;
+    const uint64_t nb = A.head->nblocks, F = A.bh->filters, total = A.bh->filt_bytes;
+    const uint64_t step = static_cast<uint64_t>(gridDim.x) * kSbThreads;
+    uint8_t *arr = A.file + A.bh->filter_off + total;
+    for (uint64_t f = static_cast<uint64_t>(blockIdx.x) * kSbThreads + threadIdx.x; f < F; f += step) {
+        const uint64_t lim = f << LV_SST_FILTER_BASE_LG;
+        uint64_t lo = 0, hi = nb;
+        for (uint32_t it = 0; it < 40 && lo < hi; ++it) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (A.boff[mid] >= lim)
+                hi = mid;
+            else
+                lo = mid + 1;
+        }
+        sb_put_fixed32(arr + 4 * f, static_cast<uint32_t>(lo < nb ? A.Fl[lo] + A.cF[lo / kSbTile] : total));
+    }
 }
 
 }  // namespace lvk
@@ -607,8 +889,9 @@ constexpr uint64_t sb_tiles(uint64_t cap) { return (cap + lvk::kSbTile - 1) / lv
 
 // The workspace for op_cap = cap and block_cap = bc, region by region: fills
 // A's workspace pointers and returns the CRC batch's sub-workspace
-// (lv_crc32c_workspace_bytes(1) bytes).
-uint8_t *sb_carve(Carve &C, uint64_t cap, uint64_t bc, lvk::SbArgs &A) {
+// (lv_crc32c_workspace_bytes(1) bytes).  bloom: lv_sst_build_bloom_device's,
+// with a third handle, a second buffer in the batch and its own regions last.
+uint8_t *sb_carve(Carve &C, uint64_t cap, uint64_t bc, lvk::SbArgs &A, bool bloom = false) {
     const uint64_t tiles = sb_tiles(cap);
     A.head = C.take<lvk::SbHead>(1);
     A.shared = C.take<uint64_t>(cap);
@@ -627,14 +910,31 @@ uint8_t *sb_carve(Carve &C, uint64_t cap, uint64_t bc, lvk::SbArgs &A) {
     A.cB = C.take<uint64_t>(tiles);
     A.cI = C.take<uint64_t>(tiles);
     A.blk_start = C.take<uint32_t>(bc);
-    A.wsh = C.take<uint64_t>(2 * (bc + 2));
-    if (uint32_t *idx = C.take<uint32_t>(4)) {  // the one-buffer batch: {offset (u64), length, crc}
+    const uint32_t nbuf = bloom ? 2 : 1;
+    A.wsh = C.take<uint64_t>(2 * (bc + 1 + nbuf));
+    if (uint32_t *idx = C.take<uint32_t>(4 * nbuf)) {  // the batch: {offsets (u64), lengths, crcs}
         A.idx_off = reinterpret_cast<uint64_t *>(idx);
-        A.idx_len = idx + 2;
-        A.idx_crc = idx + 3;
+        A.idx_len = idx + 2 * nbuf;
+        A.idx_crc = idx + 3 * nbuf;
     }
-    return C.take<uint8_t>(lv_crc32c_workspace_bytes(1));
+    uint8_t *crc_ws = C.take<uint8_t>(lv_crc32c_workspace_bytes(nbuf));
+    if (bloom) {
+        A.bh = C.take<lvk::SbBloomHead>(1);
+        A.boff = C.take<uint64_t>(cap);
+        A.bstart = C.take<uint32_t>(cap);
+        A.Fn = C.take<uint32_t>(cap);
+        A.Fl = C.take<uint64_t>(cap);
+        A.cF = C.take<uint64_t>(tiles);
+    }
+    return crc_ws;
 }
+
+// lv_sst_build_device (bloom == NULL) and lv_sst_build_bloom_device.
+int sb_build(const uint8_t *d_payload, size_t payload_bytes, const lv_wb_op *d_ops, const uint32_t *d_order,
+             const lv_mt_totals *d_mt_totals, size_t op_cap, const lv_sst_build_options *opt,
+             const lv_sst_bloom_options *bloom, uint8_t *d_file, uint64_t file_cap, uint64_t *d_handles,
+             size_t block_cap, lv_sst_build_totals *d_totals, lv_sst_bloom_totals *d_bloom_totals, uint32_t flags,
+             void *d_workspace, size_t workspace_bytes, void *stream);
 
 }  // namespace
 
@@ -648,11 +948,48 @@ size_t lv_sst_build_workspace_bytes(size_t op_cap, size_t block_cap) {
     return C.at;
 }
 
+size_t lv_sst_build_bloom_workspace_bytes(size_t op_cap, size_t block_cap) {
+    if (op_cap > kMaxOpCap || block_cap > kMaxBlockCap) return 0;
+    lvk::SbArgs A{};
+    Carve C{nullptr};
+    sb_carve(C, op_cap, block_cap, A, true);
+    return C.at;
+}
+
 int lv_sst_build_device(const uint8_t *d_payload, size_t payload_bytes, const lv_wb_op *d_ops, const uint32_t *d_order,
                         const lv_mt_totals *d_mt_totals, size_t op_cap, const lv_sst_build_options *opt,
                         uint8_t *d_file, uint64_t file_cap, uint64_t *d_handles, size_t block_cap,
                         lv_sst_build_totals *d_totals, uint32_t flags, void *d_workspace, size_t workspace_bytes,
                         void *stream) {
+    return sb_build(d_payload, payload_bytes, d_ops, d_order, d_mt_totals, op_cap, opt, nullptr, d_file, file_cap,
+                    d_handles, block_cap, d_totals, nullptr, flags, d_workspace, workspace_bytes, stream);
+}
+
+int lv_sst_build_bloom_device(const uint8_t *d_payload, size_t payload_bytes, const lv_wb_op *d_ops,
+                              const uint32_t *d_order, const lv_mt_totals *d_mt_totals, size_t op_cap,
+                              const lv_sst_build_options *opt, const lv_sst_bloom_options *bloom, uint8_t *d_file,
+                              uint64_t file_cap, uint64_t *d_handles, size_t block_cap, lv_sst_build_totals *d_totals,
+                              lv_sst_bloom_totals *d_bloom_totals, uint32_t flags, void *d_workspace,
+                              size_t workspace_bytes, void *stream) {
+    g_err.clear();
+    if (!bloom) return set_err(LV_ERR_INVALID, "null bloom options");
+    if (bloom->bits_per_key < 1 || bloom->bits_per_key > 64) return set_err(LV_ERR_INVALID, "bits_per_key must be in [1, 64]");
+    if (bloom->reserved) return set_err(LV_ERR_INVALID, "bloom options: reserved must be 0");
+    if (!d_bloom_totals) return set_err(LV_ERR_INVALID, "null d_bloom_totals");
+    if (misaligned(d_bloom_totals, 8)) return set_err(LV_ERR_INVALID, "d_bloom_totals must be 8-byte aligned");
+    return sb_build(d_payload, payload_bytes, d_ops, d_order, d_mt_totals, op_cap, opt, bloom, d_file, file_cap,
+                    d_handles, block_cap, d_totals, d_bloom_totals, flags, d_workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+int sb_build(const uint8_t *d_payload, size_t payload_bytes, const lv_wb_op *d_ops, const uint32_t *d_order,
+             const lv_mt_totals *d_mt_totals, size_t op_cap, const lv_sst_build_options *opt,
+             const lv_sst_bloom_options *bloom, uint8_t *d_file, uint64_t file_cap, uint64_t *d_handles,
+             size_t block_cap, lv_sst_build_totals *d_totals, lv_sst_bloom_totals *d_bloom_totals, uint32_t flags,
+             void *d_workspace, size_t workspace_bytes, void *stream) {
     g_err.clear();
     if (flags) return set_err(LV_ERR_INVALID, "unknown flag bits (none are defined)");
     const uint32_t bs = opt ? opt->block_size : LV_SST_DEFAULT_BLOCK_SIZE;
@@ -679,9 +1016,10 @@ int lv_sst_build_device(const uint8_t *d_payload, size_t payload_bytes, const lv
     if (misaligned(d_workspace, 16)) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
     lvk::SbArgs A{};
     Carve C{static_cast<uint8_t *>(d_workspace)};
-    uint8_t *crc_ws = sb_carve(C, op_cap, block_cap, A);
+    uint8_t *crc_ws = sb_carve(C, op_cap, block_cap, A, bloom != nullptr);
     if (workspace_bytes < C.at) return set_err(LV_ERR_INVALID, "workspace too small");
-    const uint64_t handle_bytes = (static_cast<uint64_t>(block_cap) + 2) * 16;
+    const uint32_t nbuf = bloom ? 2 : 1;  // the CRC batch's buffers; block_cap + 1 + nbuf handle pairs
+    const uint64_t handle_bytes = (static_cast<uint64_t>(block_cap) + 1 + nbuf) * 16;
     const struct {
         const void *p;
         uint64_t bytes;
@@ -712,6 +1050,8 @@ int lv_sst_build_device(const uint8_t *d_payload, size_t payload_bytes, const lv
     A.handles = d_handles;
     A.block_cap = block_cap;
     A.totals = d_totals;
+    A.bpk = bloom ? bloom->bits_per_key : 0;
+    A.btotals = d_bloom_totals;
 
     const dim3 b(lvk::kSbThreads);
     const uint32_t tiles = static_cast<uint32_t>(sb_tiles(op_cap));
@@ -727,27 +1067,44 @@ int lv_sst_build_device(const uint8_t *d_payload, size_t payload_bytes, const lv
         hipLaunchKernelGGL(lvk::sb_carry, dim3(1), b, 0, s, A, 1u);
         hipLaunchKernelGGL(lvk::sb_index, dim3(tiles), b, 0, s, A);
         hipLaunchKernelGGL(lvk::sb_carry, dim3(1), b, 0, s, A, 2u);
+        if (bloom) {
+            hipLaunchKernelGGL(lvk::sb_bloom_sizes, dim3(tiles), b, 0, s, A);
+            hipLaunchKernelGGL(lvk::sb_carry, dim3(1), b, 0, s, A, 3u);
+        }
     }
     hipLaunchKernelGGL(lvk::sb_plan, dim3(1), dim3(1), 0, s, A);
     if (tiles) hipLaunchKernelGGL(lvk::sb_emit, dim3(eg), b, 0, s, A);
-    const uint32_t hg = static_cast<uint32_t>((static_cast<uint64_t>(block_cap) + 2 + lvk::kSbThreads - 1) / lvk::kSbThreads);
+    if (tiles && bloom) {
+        // a wave per data block, a lane per window: grid-stride loops over capped grids
+        const uint32_t wg = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(op_cap) + kWaves - 1) / kWaves, 1024));
+        const uint32_t og = static_cast<uint32_t>(
+            std::min<uint64_t>((file_cap >> LV_SST_FILTER_BASE_LG) / lvk::kSbThreads + 1, 1024));
+        hipLaunchKernelGGL(lvk::sb_bloom_emit, dim3(wg), b, 0, s, A);
+        hipLaunchKernelGGL(lvk::sb_bloom_big, dim3(wg), b, 0, s, A);
+        hipLaunchKernelGGL(lvk::sb_bloom_offsets, dim3(og), b, 0, s, A);
+    }
+    const uint32_t hg = static_cast<uint32_t>((static_cast<uint64_t>(block_cap) + 1 + nbuf + lvk::kSbThreads - 1) / lvk::kSbThreads);
     hipLaunchKernelGGL(lvk::sb_tail, dim3(hg), b, 0, s, A);
     if (int rc = check_launch()) return rc;
     if (tiles && file_cap) {
         // the trailers: the seal's own kernel over the padded handles (data blocks and metaindex) ...
         if (int rc = lvgpu_internal::launch_sst_blocks(true, d_file, file_cap, A.wsh, nullptr,
-                                                       static_cast<size_t>(block_cap) + 2, nullptr, nullptr, stream))
+                                                       static_cast<size_t>(block_cap) + 1 + nbuf, nullptr, nullptr, stream))
             return rc;
-        // ... and the index block as a one-buffer batch (an empty one when nothing was written)
-        if (int rc = lv_crc32c_batch_device_ws(d_file, A.idx_off, A.idx_len, nullptr, A.idx_crc, 1, LV_CRC_MASK,
-                                               crc_ws, lv_crc32c_workspace_bytes(1), stream))
+        // ... and the index block (with a filter policy, the filter block too) as a batch of the
+        // offsets API (an empty one when nothing was written)
+        if (int rc = lv_crc32c_batch_device_ws(d_file, A.idx_off, A.idx_len, nullptr, A.idx_crc, nbuf, LV_CRC_MASK,
+                                               crc_ws, lv_crc32c_workspace_bytes(nbuf), stream))
             return rc;
         hipLaunchKernelGGL(lvk::sb_index_trailer, dim3(1), dim3(1), 0, s, A);
         if (int rc = check_launch()) return rc;
     }
-    g_kernel = "sb_init+sb_sizes+sb_carry+sb_next+sb_reach+sb_layout+sb_index+sb_plan+sb_emit+sb_tail+"
-               "sst_blocks_kernel<seal>+crc32c_fused_small_kernel+sb_index_trailer";
+    g_kernel = bloom ? "sb_init+sb_sizes+sb_carry+sb_next+sb_reach+sb_layout+sb_index+sb_bloom_sizes+sb_plan+sb_emit+"
+                       "sb_bloom_emit+sb_bloom_big+sb_bloom_offsets+sb_tail+sst_blocks_kernel<seal>+"
+                       "crc32c_fused_small_kernel+sb_index_trailer"
+                     : "sb_init+sb_sizes+sb_carry+sb_next+sb_reach+sb_layout+sb_index+sb_plan+sb_emit+sb_tail+"
+                       "sst_blocks_kernel<seal>+crc32c_fused_small_kernel+sb_index_trailer";
     return LV_OK;
 }
 
-}  // extern "C"
+}  // namespace

@@ -50,4 +50,44 @@ int lv_sst_get_host(const uint8_t *file, const lv_sst_table *table, const uint8_
     return 0;
 }
 
+// ---- the filter block ("Bloom filter blocks") ----
+
+uint32_t lv_bloom_hash(const uint8_t *key, size_t n) { return lvr::hash(key, n, lvr::kBloomSeed); }
+
+int lv_bloom_key_may_match(const uint8_t *key, size_t key_len, const uint8_t *filter, size_t filter_len) {
+    if (filter_len < 2) return 0;
+    return lvr::bloom_may_match(filter, filter_len, lv_bloom_hash(key, key_len)) ? 1 : 0;
+}
+
+int lv_sst_bloom_open_host(const uint8_t *file, const lv_sst_table *table, lv_sst_bloom *bloom) {
+    if (!table || !bloom || (!file && table->file_bytes)) return LV_ERR_INVALID;
+    lv_sst_bloom b{};
+    if (table->status)
+        b.why = LV_SST_BLOOM_TABLE;
+    else if (!table->file_bytes)
+        b.why = LV_SST_BLOOM_EMPTY;
+    else
+        lvr::bloom_open(file, table->file_bytes, table->metaindex_offset, table->metaindex_size, &b);
+    *bloom = b;
+    return 0;
+}
+
+int lv_sst_get_bloom_host(const uint8_t *file, const lv_sst_table *table, const lv_sst_bloom *bloom,
+                          const uint8_t *qkey, size_t qkey_len, uint64_t seq, lv_sst_get_result *result) {
+    if (!table || !bloom || !result || (!file && table->file_bytes) || (!qkey && qkey_len) || qkey_len > 0xffffffffull)
+        return LV_ERR_INVALID;
+    lv_sst_get_result r{};
+    if (table->status) {
+        r.status = LV_SST_GET_NO_TABLE;
+    } else if (seq > LV_MT_MAX_SEQUENCE) {
+        r.status = LV_SST_GET_BAD_SEQ;
+    } else {
+        const lvr::Target t{qkey, static_cast<uint32_t>(qkey_len), (seq << 8) | LV_WB_TYPE_VALUE};
+        r.status = lvr::get(file, table->file_bytes, table->index_offset, table->index_size, t, &r,
+                            bloom->present == 1 ? bloom : nullptr);
+    }
+    *result = r;
+    return 0;
+}
+
 }  // extern "C"

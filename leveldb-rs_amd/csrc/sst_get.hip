@@ -20,6 +20,10 @@
 //   sg_get       one lane per query: the index seek, the block seek and
 //                SaveValue.  Its state is a handful of registers whatever the
 //                key lengths; a wave's lanes diverge where their blocks do.
+//                sg_get<true> (lv_sst_get_bloom_device) asks the filter of
+//                *d_bloom between the two seeks.
+//   so_bloom     (lv_sst_bloom_open_device) one thread: Table::ReadMeta and
+//                ReadFilter; writes every field of *d_bloom.
 //
 // No workspace; the launch sequences depend only on host values (block_cap,
 // file_cap, whether d_handles is NULL; nq).  No workgroup waits on another.
@@ -110,8 +114,12 @@ struct SgArgs {
     const uint64_t *q_seq;
     uint64_t nq;
     lv_sst_get_result *results;
+    const lv_sst_bloom *bloom;  // sg_get<true>: lv_sst_get_bloom_device
 };
 
+// kBloom: the filter *G.bloom is asked before a data block is touched (when it
+// says present; lvr::may_match checks its offsets against the file again).
+template <bool kBloom>
 __global__ __launch_bounds__(kSgThreads) void sg_get(const SgArgs G) {
     const uint64_t q = static_cast<uint64_t>(blockIdx.x) * kSgThreads + threadIdx.x;
     if (q >= G.nq) return;
@@ -126,9 +134,28 @@ __global__ __launch_bounds__(kSgThreads) void sg_get(const SgArgs G) {
         r.status = LV_SST_GET_BAD_QUERY;
     } else {
         const lvr::Target t{G.qkeys + qo, ql, (seq << 8) | LV_WB_TYPE_VALUE};
-        r.status = lvr::get(G.file, fb, G.table->index_offset, G.table->index_size, t, &r);
+        if constexpr (kBloom) {
+            const lv_sst_bloom b = *G.bloom;
+            r.status = lvr::get(G.file, fb, G.table->index_offset, G.table->index_size, t, &r,
+                                b.present == 1 ? &b : nullptr);
+        } else {
+            r.status = lvr::get(G.file, fb, G.table->index_offset, G.table->index_size, t, &r);
+        }
     }
     G.results[q] = r;
+}
+
+// lv_sst_bloom_open_device: one thread, Table::ReadMeta / ReadFilter.
+__global__ void so_bloom(const uint8_t *file, uint64_t file_cap, const lv_sst_table *table, lv_sst_bloom *bloom) {
+    lv_sst_bloom b{};
+    const uint64_t fb = table->file_bytes;
+    if (table->status || fb > file_cap)
+        b.why = LV_SST_BLOOM_TABLE;
+    else if (!fb)
+        b.why = LV_SST_BLOOM_EMPTY;
+    else
+        lvr::bloom_open(file, fb, table->metaindex_offset, table->metaindex_size, &b);
+    *bloom = b;
 }
 
 }  // namespace lvk
@@ -182,13 +209,20 @@ int lv_sst_open_device(const uint8_t *d_file, uint64_t file_cap, const uint64_t 
     return check_launch();
 }
 
-int lv_sst_get_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_table *d_table, const uint8_t *d_qkeys,
-                      size_t qkeys_bytes, const uint64_t *d_q_off, const uint32_t *d_q_len, const uint64_t *d_q_seq,
-                      size_t nq, lv_sst_get_result *d_results, uint32_t flags, void *stream) {
+}  // extern "C"
+
+namespace {
+
+// lv_sst_get_device (d_bloom == NULL, bloom false) and lv_sst_get_bloom_device.
+int sg_launch(const uint8_t *d_file, uint64_t file_cap, const lv_sst_table *d_table, const lv_sst_bloom *d_bloom,
+              bool bloom, const uint8_t *d_qkeys, size_t qkeys_bytes, const uint64_t *d_q_off, const uint32_t *d_q_len,
+              const uint64_t *d_q_seq, size_t nq, lv_sst_get_result *d_results, uint32_t flags, void *stream) {
     g_err.clear();
     if (flags) return set_err(LV_ERR_INVALID, "unknown flag bits (none are defined)");
     if (!d_table) return set_err(LV_ERR_INVALID, "null d_table");
     if (misaligned(d_table, 8)) return set_err(LV_ERR_INVALID, "d_table must be 8-byte aligned");
+    if (bloom && !d_bloom) return set_err(LV_ERR_INVALID, "null d_bloom");
+    if (misaligned(d_bloom, 8)) return set_err(LV_ERR_INVALID, "d_bloom must be 8-byte aligned");
     if (!d_file && file_cap) return set_err(LV_ERR_INVALID, "null d_file");
     if (!d_qkeys && qkeys_bytes) return set_err(LV_ERR_INVALID, "null d_qkeys");
     if (nq > kMaxNq) return set_err(LV_ERR_INVALID, "nq too large for one call (at most 2^32 - 2)");
@@ -214,9 +248,49 @@ int lv_sst_get_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_tab
     G.q_seq = d_q_seq;
     G.nq = nq;
     G.results = d_results;
+    G.bloom = d_bloom;
     const uint32_t grid = static_cast<uint32_t>((static_cast<uint64_t>(nq) + lvk::kSgThreads - 1) / lvk::kSgThreads);
-    hipLaunchKernelGGL(lvk::sg_get, dim3(grid), dim3(lvk::kSgThreads), 0, static_cast<hipStream_t>(stream), G);
-    g_kernel = "sg_get";
+    if (bloom)
+        hipLaunchKernelGGL(lvk::sg_get<true>, dim3(grid), dim3(lvk::kSgThreads), 0, static_cast<hipStream_t>(stream), G);
+    else
+        hipLaunchKernelGGL(lvk::sg_get<false>, dim3(grid), dim3(lvk::kSgThreads), 0, static_cast<hipStream_t>(stream), G);
+    g_kernel = bloom ? "sg_get<bloom>" : "sg_get";
+    return check_launch();
+}
+
+}  // namespace
+
+extern "C" {
+
+int lv_sst_get_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_table *d_table, const uint8_t *d_qkeys,
+                      size_t qkeys_bytes, const uint64_t *d_q_off, const uint32_t *d_q_len, const uint64_t *d_q_seq,
+                      size_t nq, lv_sst_get_result *d_results, uint32_t flags, void *stream) {
+    return sg_launch(d_file, file_cap, d_table, nullptr, false, d_qkeys, qkeys_bytes, d_q_off, d_q_len, d_q_seq, nq,
+                     d_results, flags, stream);
+}
+
+int lv_sst_get_bloom_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_table *d_table,
+                            const lv_sst_bloom *d_bloom, const uint8_t *d_qkeys, size_t qkeys_bytes,
+                            const uint64_t *d_q_off, const uint32_t *d_q_len, const uint64_t *d_q_seq, size_t nq,
+                            lv_sst_get_result *d_results, uint32_t flags, void *stream) {
+    return sg_launch(d_file, file_cap, d_table, d_bloom, true, d_qkeys, qkeys_bytes, d_q_off, d_q_len, d_q_seq, nq,
+                     d_results, flags, stream);
+}
+
+int lv_sst_bloom_open_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_table *d_table,
+                             lv_sst_bloom *d_bloom, uint32_t flags, void *stream) {
+    g_err.clear();
+    if (flags) return set_err(LV_ERR_INVALID, "unknown flag bits (none are defined)");
+    if (!d_table) return set_err(LV_ERR_INVALID, "null d_table");
+    if (misaligned(d_table, 8)) return set_err(LV_ERR_INVALID, "d_table must be 8-byte aligned");
+    if (!d_bloom) return set_err(LV_ERR_INVALID, "null d_bloom");
+    if (misaligned(d_bloom, 8)) return set_err(LV_ERR_INVALID, "d_bloom must be 8-byte aligned");
+    if (!d_file && file_cap) return set_err(LV_ERR_INVALID, "null d_file");
+    DevCtx *c = nullptr;
+    if (int rc = current_ctx(&c)) return rc;
+    hipLaunchKernelGGL(lvk::so_bloom, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), d_file, file_cap, d_table,
+                       d_bloom);
+    g_kernel = "so_bloom";
     return check_launch();
 }
 

@@ -24,6 +24,18 @@ block-trailer seal/verify and the SSTable build over include/lvgpu/table.h.
                                       totals; .memtable() is what build_device and
                                       lvgpu.memtable.get_device take), asynchronous
                                       until .sync()
+    bloom_hash / bloom_filter_bytes / bloom_create_filter / bloom_key_may_match
+                                      the lv_bloom_* host scalars
+    build_bloom_host(...) / build_bloom_device(table, bits_per_key)
+                                      lv_sst_build_bloom_*: the build with a filter
+                                      block; a BuiltBloom (data_blocks + 3 handles,
+                                      .sync_bloom_totals())
+    bloom_open_host(file, table) / bloom_open_device(opened)
+                                      lv_sst_bloom_open_*: the lv_sst_bloom as a dict /
+                                      as an int64[8] CUDA tensor (bloom_dict reads it)
+    get_bloom_host(...) / get_bloom_device(opened, bloom, qkeys, ...)
+                                      lv_sst_get_bloom_*: the get that asks the filter
+                                      first; reserved == GET_FILTERED where it said no
 """
 from __future__ import annotations
 
@@ -270,6 +282,8 @@ class Built:
     """Outputs of build_device, CUDA tensors written asynchronously: file_t
     (uint8, file_cap bytes and the guard), handles_t (int64, block_cap + 2
     pairs and the guard) and totals (int64[8], BUILD_TOTALS)."""
+    _extra = 2  # the handle pairs behind the data blocks'
+    _name = "lv_sst_build_device"
 
     def __init__(self, file_t, file_cap, handles_t, block_cap, totals, keep):
         self.file_t, self.file_cap, self.handles_t, self.block_cap, self.totals = file_t, file_cap, handles_t, block_cap, totals
@@ -288,7 +302,7 @@ class Built:
         st = self._tot["status"]
         if st and check:
             names = "|".join(n for b, n in BUILD_STATUS.items() if st & b)
-            raise LvError(f"lv_sst_build_device: status {names} (totals {self._tot})")
+            raise LvError(f"{self._name}: status {names} (totals {self._tot})")
         return self._tot
 
     def file(self) -> bytes:
@@ -299,7 +313,7 @@ class Built:
     def handles(self) -> list:
         """The data_blocks + 2 handles as (offset, size) pairs (synchronises)."""
         t = self.sync_totals()
-        n = t["data_blocks"] + 2 if t["file_bytes"] else 0
+        n = t["data_blocks"] + self._extra if t["file_bytes"] else 0
         h = self.handles_t[: 2 * n].cpu().numpy().view(np.uint64)
         return [(int(h[2 * i]), int(h[2 * i + 1])) for i in range(n)]
 
@@ -307,13 +321,14 @@ class Built:
         """The written handles as an (n, 2) int64 CUDA tensor for verify_blocks
         (synchronises for the count)."""
         t = self.sync_totals()
-        n = t["data_blocks"] + 2 if t["file_bytes"] else 0
+        n = t["data_blocks"] + self._extra if t["file_bytes"] else 0
         return self.handles_t[: 2 * n].view(n, 2)
 
 
 def build_device(table, *, block_size=None, restart_interval=None, file_cap=None, block_cap=None, workspace=None,
-                 stream=None, fill=None, guard: int = 0, flags: int = 0):
-    """lv_sst_build_device over a lvgpu.memtable.Table (its payload, ops,
+                 stream=None, fill=None, guard: int = 0, flags: int = 0, bits_per_key=None, bloom_reserved: int = 0):
+    """lv_sst_build_device (with bits_per_key, lv_sst_build_bloom_device: see
+    build_bloom_device) over a lvgpu.memtable.Table (its payload, ops,
     order and totals, read on the device).  file_cap defaults to file_bound of
     the payload and op_cap, block_cap to op_cap (a block holds at least one
     entry).  fill, a byte value, initialises d_file and d_handles with it first
@@ -323,15 +338,20 @@ def build_device(table, *, block_size=None, restart_interval=None, file_cap=None
     L = _bind_build()
     dev = table.payload.device
     op_cap = int(table.op_cap)
+    bloom = bits_per_key is not None
+    if bloom:
+        L = _bind_bloom()
+        bopt = BloomOptions(bits_per_key, bloom_reserved)
     if file_cap is None:
-        file_cap = file_bound(table.payload.numel(), op_cap, block_size, restart_interval)
+        file_cap = (bloom_file_bound(table.payload.numel(), op_cap, bits_per_key) if bloom
+                    else file_bound(table.payload.numel(), op_cap, block_size, restart_interval))
     if block_cap is None:
         block_cap = op_cap
     if workspace is None:
-        workspace = torch.empty(max(L.lv_sst_build_workspace_bytes(op_cap, block_cap), 16), dtype=torch.uint8,
-                                device=dev)
+        need = (L.lv_sst_build_bloom_workspace_bytes if bloom else L.lv_sst_build_workspace_bytes)(op_cap, block_cap)
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     fbytes = (max(file_cap, 16) + guard + 15) & ~15
-    hbytes = (16 * (block_cap + 2) + guard + 7) & ~7
+    hbytes = (16 * (block_cap + (3 if bloom else 2)) + guard + 7) & ~7
     if fill is None:
         file_t = torch.empty(fbytes, dtype=torch.uint8, device=dev)
         handles_t = torch.empty(hbytes, dtype=torch.uint8, device=dev).view(torch.int64)
@@ -340,6 +360,20 @@ def build_device(table, *, block_size=None, restart_interval=None, file_cap=None
         handles_t = torch.full((hbytes,), fill, dtype=torch.uint8, device=dev).view(torch.int64)
     totals = torch.empty(len(BUILD_TOTALS), dtype=torch.int64, device=dev)
     opt = _options(block_size, restart_interval)
+    if bloom:
+        bloom_totals = torch.empty(len(BLOOM_TOTALS), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            rc = L.lv_sst_build_bloom_device(_dev_ptr(table.payload, "payload"), table.payload.numel(),
+                                             _dev_ptr(table.ops_t, "ops"), _dev_ptr(table.order_t, "order"),
+                                             _dev_ptr(table.totals, "mt_totals"), op_cap,
+                                             ctypes.byref(opt) if opt else None, ctypes.byref(bopt),
+                                             _dev_ptr(file_t, "file"), file_cap, _dev_ptr(handles_t, "handles"),
+                                             block_cap, _dev_ptr(totals, "totals"),
+                                             _dev_ptr(bloom_totals, "bloom_totals"), flags,
+                                             _dev_ptr(workspace, "workspace"), workspace.numel(), _stream_ptr(stream))
+        if rc != 0:
+            raise LvError(f"lv_sst_build_bloom_device: {lib().lv_last_error().decode()}")
+        return BuiltBloom(file_t, file_cap, handles_t, block_cap, totals, (table, workspace), bloom_totals)
     with torch.cuda.device(dev):  # the C call runs on the current device
         rc = L.lv_sst_build_device(_dev_ptr(table.payload, "payload"), table.payload.numel(),
                                    _dev_ptr(table.ops_t, "ops"), _dev_ptr(table.order_t, "order"),
@@ -759,3 +793,254 @@ def scan_device(opened, prev=None, *, arena_cap=None, op_cap=None, block_cap=Non
         raise LvError(f"lv_sst_scan_device: {lib().lv_last_error().decode()}")
     return Scanned(arena_t, arena_cap, ops_t, op_cap, block_cap, totals, order_t if order else None,
                    mt_totals if order else None, (opened, prev, workspace))
+
+
+# ---- Bloom filter blocks: lv_bloom_*, lv_sst_build_bloom_*, lv_sst_bloom_open_*, lv_sst_get_bloom_* ----
+BLOOM_NAME = b"filter.leveldb.BuiltinBloomFilter2"  # LV_SST_BLOOM_NAME
+FILTER_BASE_LG = 11                                  # LV_SST_FILTER_BASE_LG
+GET_FILTERED = 1                                     # lv_sst_get_result.reserved of a query the filter rejected
+BLOOM_TOTALS = ("filter_offset", "filter_size", "filters", "filter_keys")
+BLOOM_FIELDS = ("filter_offset", "filter_size", "array_offset", "num", "base_lg", "present", "why", "reserved")
+BLOOM_WHY = {0: "", 1: "TABLE", 2: "EMPTY", 3: "BAD_METAINDEX", 4: "NO_ENTRY", 5: "BAD_HANDLE", 6: "BAD_TYPE",
+             7: "SHORT", 8: "BAD_ARRAY"}  # LV_SST_BLOOM_*
+SB_BLOOM_LDS = 2048  # csrc/sst_build.hip kSbBloomLds: filter bytes a wave holds in LDS; larger ones take the atomic path
+
+
+class BloomOptions(ctypes.Structure):
+    """lv_sst_bloom_options."""
+    _fields_ = [("bits_per_key", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class BloomTotals(ctypes.Structure):
+    """lv_sst_bloom_totals."""
+    _fields_ = [(n, ctypes.c_uint64) for n in BLOOM_TOTALS]
+
+
+class SstBloom(ctypes.Structure):
+    """lv_sst_bloom."""
+    _fields_ = [(n, ctypes.c_uint64) for n in BLOOM_FIELDS]
+
+
+_bloom_bound = False
+
+
+def _bind_bloom():
+    global _bloom_bound
+    L = _bind_get()
+    _bind_build()
+    if not _bloom_bound:
+        vp, sz, u64, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32
+        L.lv_bloom_hash.restype = u32
+        L.lv_bloom_hash.argtypes = [vp, sz]
+        L.lv_bloom_filter_bytes.restype = sz
+        L.lv_bloom_filter_bytes.argtypes = [sz, u32]
+        L.lv_bloom_create_filter.restype = ctypes.c_int
+        L.lv_bloom_create_filter.argtypes = [vp, vp, vp, sz, u32, vp]
+        L.lv_bloom_key_may_match.restype = ctypes.c_int
+        L.lv_bloom_key_may_match.argtypes = [vp, sz, vp, sz]
+        L.lv_sst_build_bloom_workspace_bytes.restype = sz
+        L.lv_sst_build_bloom_workspace_bytes.argtypes = [sz, sz]
+        L.lv_sst_build_bloom_file_bound.restype = u64
+        L.lv_sst_build_bloom_file_bound.argtypes = [u64, u64, vp, vp]
+        L.lv_sst_build_bloom_device.restype = ctypes.c_int
+        L.lv_sst_build_bloom_device.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp, u64, vp, sz, vp, vp, u32, vp, sz, vp]
+        L.lv_sst_build_bloom_host.restype = ctypes.c_int
+        L.lv_sst_build_bloom_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, u64, vp, sz, vp, vp]
+        L.lv_sst_bloom_open_device.restype = ctypes.c_int
+        L.lv_sst_bloom_open_device.argtypes = [vp, u64, vp, vp, u32, vp]
+        L.lv_sst_bloom_open_host.restype = ctypes.c_int
+        L.lv_sst_bloom_open_host.argtypes = [vp, vp, vp]
+        L.lv_sst_get_bloom_device.restype = ctypes.c_int
+        L.lv_sst_get_bloom_device.argtypes = [vp, u64, vp, vp, vp, sz, vp, vp, vp, sz, vp, u32, vp]
+        L.lv_sst_get_bloom_host.restype = ctypes.c_int
+        L.lv_sst_get_bloom_host.argtypes = [vp, vp, vp, vp, sz, u64, vp]
+        _bloom_bound = True
+    return L
+
+
+def bloom_hash(key) -> int:
+    """lv_bloom_hash: lv_hash(key, 0xbc9f1d34)."""
+    kb = bytes(key)
+    return int(_bind_bloom().lv_bloom_hash(kb, len(kb)))
+
+
+def bloom_filter_bytes(n: int, bits_per_key: int) -> int:
+    return int(_bind_bloom().lv_bloom_filter_bytes(n, bits_per_key))
+
+
+def bloom_create_filter(keys, bits_per_key: int) -> bytes:
+    """lv_bloom_create_filter over a list of keys (packed with one gap byte
+    between them, so that they sit at every alignment)."""
+    L = _bind_bloom()
+    blob, off, ln = bytearray(), [], []
+    for k in keys:
+        blob += b"\xee"
+        off.append(len(blob))
+        ln.append(len(k))
+        blob += bytes(k)
+    off = np.array(off, dtype=np.uint64)
+    ln = np.array(ln, dtype=np.uint32)
+    out = ctypes.create_string_buffer(L.lv_bloom_filter_bytes(len(keys), bits_per_key) + 8)
+    out.raw = b"\xa5" * len(out)
+    rc = L.lv_bloom_create_filter(bytes(blob), off.ctypes.data if len(keys) else None,
+                                  ln.ctypes.data if len(keys) else None, len(keys), bits_per_key, out)
+    if rc != 0:
+        raise LvError(f"lv_bloom_create_filter: {rc}")
+    assert out.raw[-8:] == b"\xa5" * 8, "lv_bloom_create_filter wrote beyond lv_bloom_filter_bytes"
+    return out.raw[:-8]
+
+
+def bloom_key_may_match(key, filt) -> bool:
+    kb, fb = bytes(key), bytes(filt)
+    return bool(_bind_bloom().lv_bloom_key_may_match(kb, len(kb), fb, len(fb)))
+
+
+def build_bloom_workspace_bytes(op_cap: int, block_cap: int) -> int:
+    return int(_bind_bloom().lv_sst_build_bloom_workspace_bytes(op_cap, block_cap))
+
+
+def bloom_file_bound(payload_bytes: int, op_cap: int, bits_per_key: int) -> int:
+    """lv_sst_build_bloom_file_bound."""
+    b = BloomOptions(bits_per_key, 0)
+    return int(_bind_bloom().lv_sst_build_bloom_file_bound(payload_bytes, op_cap, None, ctypes.byref(b)))
+
+
+def build_bloom_host(payload, ops, order, mt_totals, bits_per_key=10, block_size=None, restart_interval=None, *,
+                     file_cap=None, block_cap=None, sizing=False, reserved=0):
+    """lv_sst_build_bloom_host: (file bytes, handles, totals dict, bloom totals
+    dict), as build_host; data_blocks + 3 handles."""
+    from .write_batch import OP_DTYPE
+    L = _bind_bloom()
+    pb = bytes(payload)
+    pbuf = ctypes.create_string_buffer(pb, max(len(pb), 1))
+    arr = np.ascontiguousarray(ops, dtype=OP_DTYPE)
+    order = np.ascontiguousarray(order, dtype=np.uint32)
+    mt = MtTotals(mt_totals["entries"], mt_totals["user_keys"], mt_totals["status"])
+    opt = _options(block_size, restart_interval)
+    bopt = BloomOptions(bits_per_key, reserved)
+    tot, btot = BuildTotals(), BloomTotals()
+
+    def call(file_p, fcap, handles_p, bcap):
+        rc = L.lv_sst_build_bloom_host(pbuf, len(pb), arr.ctypes.data if arr.size else None,
+                                       order.ctypes.data if order.size else None, ctypes.byref(mt),
+                                       ctypes.byref(opt) if opt else None, ctypes.byref(bopt), file_p, fcap, handles_p,
+                                       bcap, ctypes.byref(tot), ctypes.byref(btot))
+        if rc != 0:
+            raise LvError(f"lv_sst_build_bloom_host: {rc}")
+        return ({n: int(getattr(tot, n)) for n in BUILD_TOTALS}, {n: int(getattr(btot, n)) for n in BLOOM_TOTALS})
+
+    if sizing or file_cap is None or block_cap is None:
+        t, bt = call(None, 0, None, 0)
+        if sizing:
+            return b"", [], t, bt
+        file_cap = t["file_bytes"] if file_cap is None else file_cap
+        block_cap = t["data_blocks"] if block_cap is None else block_cap
+    fbuf = np.full(file_cap + 64, 0xA5, dtype=np.uint8)
+    hs = np.full(2 * (block_cap + 3) + 8, HANDLE_CANARY, dtype=np.uint64)
+    t, bt = call(fbuf.ctypes.data if file_cap else None, file_cap, hs.ctypes.data, block_cap)
+    if t["status"]:
+        return fbuf.tobytes(), hs, t, bt
+    assert (fbuf[t["file_bytes"]:] == 0xA5).all(), "lv_sst_build_bloom_host wrote at or beyond file_bytes"
+    nh = t["data_blocks"] + 3 if t["file_bytes"] else 0
+    assert (hs[2 * nh:] == HANDLE_CANARY).all(), "lv_sst_build_bloom_host wrote handles beyond its count"
+    return fbuf[: t["file_bytes"]].tobytes(), [(int(hs[2 * i]), int(hs[2 * i + 1])) for i in range(nh)], t, bt
+
+
+class BuiltBloom(Built):
+    """Outputs of build_bloom_device: a Built with data_blocks + 3 handles and
+    bloom_totals (int64[4], BLOOM_TOTALS)."""
+    _extra = 3
+    _name = "lv_sst_build_bloom_device"
+
+    def __init__(self, file_t, file_cap, handles_t, block_cap, totals, keep, bloom_totals):
+        super().__init__(file_t, file_cap, handles_t, block_cap, totals, keep)
+        self.bloom_totals = bloom_totals
+
+    def sync_bloom_totals(self) -> dict:
+        self.sync_totals(check=False)
+        return dict(zip(BLOOM_TOTALS, (int(v) for v in self.bloom_totals.cpu().numpy().view(np.uint64))))
+
+
+def build_bloom_device(table, bits_per_key=10, **kw):
+    """lv_sst_build_bloom_device over a lvgpu.memtable.Table: build_device's
+    keywords; file_cap defaults to bloom_file_bound.  Returns a BuiltBloom."""
+    return build_device(table, bits_per_key=bits_per_key, **kw)
+
+
+def bloom_open_host(file, table) -> dict:
+    """lv_sst_bloom_open_host over the bytes `file` and the table dict of
+    open_host: the lv_sst_bloom as a dict."""
+    L = _bind_bloom()
+    t = SstTable(*[int(table[n]) for n in TABLE_FIELDS])
+    b = SstBloom()
+    fb = bytes(file)
+    rc = L.lv_sst_bloom_open_host(fb, ctypes.byref(t), ctypes.byref(b))
+    if rc != 0:
+        raise LvError(f"lv_sst_bloom_open_host: {rc}")
+    return {n: int(getattr(b, n)) for n in BLOOM_FIELDS}
+
+
+def get_bloom_host(file, table, bloom, key, seq) -> dict:
+    """lv_sst_get_bloom_host for one query: a dict of the result's fields."""
+    L = _bind_bloom()
+    t = SstTable(*[int(table[n]) for n in TABLE_FIELDS])
+    b = SstBloom(*[int(bloom[n]) for n in BLOOM_FIELDS])
+    r = SstGetResult()
+    kb = bytes(key)
+    rc = L.lv_sst_get_bloom_host(file if isinstance(file, bytes) else bytes(file), ctypes.byref(t), ctypes.byref(b), kb,
+                                 len(kb), seq, ctypes.byref(r))
+    if rc != 0:
+        raise LvError(f"lv_sst_get_bloom_host: {rc}")
+    return {n: int(getattr(r, n)) for n, _ in SstGetResult._fields_}
+
+
+def bloom_open_device(opened, *, bloom=None, stream=None, flags: int = 0):
+    """lv_sst_bloom_open_device over an Opened: the lv_sst_bloom as an int64[8]
+    CUDA tensor (BLOOM_FIELDS), written asynchronously on `stream`.  bloom
+    reuses an earlier call's tensor."""
+    torch = _torch()
+    L = _bind_bloom()
+    dev = opened.file_t.device
+    if bloom is None:
+        bloom = torch.empty(len(BLOOM_FIELDS), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.lv_sst_bloom_open_device(_dev_ptr(opened.file_t, "file") if opened.file_cap else None, opened.file_cap,
+                                        _dev_ptr(opened.table, "table"), _dev_ptr(bloom, "bloom"), flags,
+                                        _stream_ptr(stream))
+    if rc != 0:
+        raise LvError(f"lv_sst_bloom_open_device: {lib().lv_last_error().decode()}")
+    return bloom
+
+
+def bloom_dict(bloom_t) -> dict:
+    """An lv_sst_bloom tensor as a dict (synchronises)."""
+    _torch().cuda.synchronize(bloom_t.device)
+    return dict(zip(BLOOM_FIELDS, (int(v) for v in bloom_t.cpu().numpy().view(np.uint64))))
+
+
+def get_bloom_device(opened, bloom, qkeys, q_off, q_len, q_seq, *, nq=None, res=None, stream=None, fill=None,
+                     guard: int = 0, flags: int = 0):
+    """lv_sst_get_bloom_device: get_device with the lv_sst_bloom tensor of
+    bloom_open_device, read on the device.  Returns a Gets."""
+    torch = _torch()
+    L = _bind_bloom()
+    dev = opened.file_t.device
+    if qkeys.dtype != torch.uint8 or q_off.dtype != torch.int64 or q_seq.dtype != torch.int64 or \
+            q_len.dtype != torch.int32:
+        raise LvError("qkeys must be uint8, q_off and q_seq int64, q_len int32")
+    nq = int(min(q_off.numel(), q_len.numel(), q_seq.numel())) if nq is None else int(nq)
+    if min(q_off.numel(), q_len.numel(), q_seq.numel()) < nq:
+        raise LvError("the query arrays must hold nq entries")
+    if res is None:
+        nbytes = (max(nq * 32, 16) + guard + 7) & ~7
+        res = (torch.empty(nbytes, dtype=torch.uint8, device=dev) if fill is None
+               else torch.full((nbytes,), fill, dtype=torch.uint8, device=dev))
+    with torch.cuda.device(dev):
+        rc = L.lv_sst_get_bloom_device(_dev_ptr(opened.file_t, "file") if opened.file_cap else None, opened.file_cap,
+                                       _dev_ptr(opened.table, "table"), _dev_ptr(bloom, "bloom"),
+                                       _dev_ptr(qkeys, "qkeys") if qkeys.numel() else None, qkeys.numel(),
+                                       _dev_ptr(q_off, "q_off"), _dev_ptr(q_len, "q_len"), _dev_ptr(q_seq, "q_seq"),
+                                       nq, _dev_ptr(res, "results"), flags, _stream_ptr(stream))
+    if rc != 0:
+        raise LvError(f"lv_sst_get_bloom_device: {lib().lv_last_error().decode()}")
+    return Gets(res, nq, (opened, bloom, qkeys, q_off, q_len, q_seq))

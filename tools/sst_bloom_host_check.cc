@@ -1,0 +1,423 @@
+// Stand-alone check of the Bloom filter blocks' host twins (csrc/sst_build.cc
+// and csrc/sst_get.cc, whose core csrc/lvk/sst_read.h is the text the kernels
+// compile too) for sanitizer builds on the CPU:
+//
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude
+//       tools/sst_bloom_host_check.cc leveldb-rs_amd/csrc/sst_get.cc leveldb-rs_amd/csrc/sst_build.cc
+//       leveldb-rs_amd/csrc/sst_format.cc leveldb-rs_amd/csrc/memtable.cc leveldb-rs_amd/csrc/crc32c_scalar.cc
+//       -o sst_bloom_host_check && ./sst_bloom_host_check [cases.bin]
+//
+// Every image and query key is a heap block of exactly its size, so a read
+// one byte outside is a heap-buffer-overflow.  Three parts:
+//   1. tables built by lv_sst_build_bloom_host: the open finds the filter the
+//      build reported, a reader without a filter policy opens the image, every
+//      stored key and its neighbours get what lv_sst_get_host gives over the
+//      same image (a stored version is never filtered at or above its own
+//      snapshot; below it the seek may land in the next block, whose filter
+//      need not hold the key; a filtered query is ABSENT there), and the data
+//      blocks are those of lv_sst_build_host;
+//   2. a few thousand random flips inside the filter block, the metaindex
+//      block and the footer through lv_sst_bloom_open_host and
+//      lv_sst_get_bloom_host, with the damaged image's own lv_sst_bloom and
+//      with the sound image's (one that was not written for this file), now
+//      and then over a truncated file: the answers stay inside the file;
+//   3. with a file argument, the cases python tests/sst_bloom_cases.py dump
+//      FILE wrote (every `why`, the flips the GPU suite replays, with the
+//      Python model's expected outputs).
+// Exits 0 when everything agrees.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "lvgpu/crc32c.h"
+#include "lvgpu/table.h"
+
+namespace lvgpu_internal {
+int set_error(int code, const char *) { return code; }
+}  // namespace lvgpu_internal
+
+namespace {
+
+int g_fail = 0;
+#define CHECK(cond)                                                          \
+    do {                                                                     \
+        if (!(cond)) {                                                       \
+            if (g_fail < 50) std::fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
+            ++g_fail;                                                        \
+        }                                                                    \
+    } while (0)
+
+struct Item {
+    std::string key, value;
+    uint64_t tag;
+};
+
+uint64_t tag(uint64_t seq, uint32_t type) { return (seq << 8) | type; }
+
+// a heap copy of exactly n bytes (NULL for none)
+uint8_t *exact(const void *p, size_t n) {
+    if (!n) return nullptr;
+    uint8_t *q = static_cast<uint8_t *>(std::malloc(n));
+    std::memcpy(q, p, n);
+    return q;
+}
+
+uint64_t g_rng = 0x9e3779b97f4a7c15ull;
+uint64_t rnd() {
+    g_rng ^= g_rng << 13;
+    g_rng ^= g_rng >> 7;
+    g_rng ^= g_rng << 17;
+    return g_rng;
+}
+
+int get(const uint8_t *file, const lv_sst_table &t, const lv_sst_bloom *b, const std::string &key, uint64_t seq,
+        lv_sst_get_result *r) {
+    uint8_t *k = exact(key.data(), key.size());
+    std::memset(r, 0xEE, sizeof *r);
+    const int rc = b ? lv_sst_get_bloom_host(file, &t, b, k, key.size(), seq, r)
+                     : lv_sst_get_host(file, &t, k, key.size(), seq, r);
+    std::free(k);
+    return rc;
+}
+
+// whatever the image says, an answer lies inside it
+void check_sane(const lv_sst_get_result &r, uint64_t fb) {
+    CHECK(r.status <= LV_SST_GET_CORRUPT && r.reserved <= LV_SST_GET_FILTERED);
+    if (r.reserved) CHECK(r.status == LV_SST_GET_ABSENT);
+    if (r.status == LV_SST_GET_FOUND) CHECK(r.val_off <= fb && r.val_len <= fb - r.val_off);
+    if (r.status != LV_SST_GET_FOUND) CHECK(r.val_off == 0 && r.val_len == 0);
+    if (r.status != LV_SST_GET_FOUND && r.status != LV_SST_GET_DELETED) CHECK(r.tag == 0 && r.block == 0);
+}
+
+void check_bloom_sane(const lv_sst_bloom &b, uint64_t fb) {
+    CHECK(b.present <= 1 && b.why <= LV_SST_BLOOM_BAD_ARRAY && b.reserved == 0 && (b.present == 1) == (b.why == 0));
+    if (b.present) {
+        CHECK(b.filter_offset <= fb && b.filter_size + 5 <= fb - b.filter_offset && b.filter_size >= 5);
+        CHECK(b.array_offset <= b.filter_size - 5 && b.num == (b.filter_size - 5 - b.array_offset) / 4 && b.base_lg < 256);
+    } else {
+        CHECK(!b.filter_offset && !b.filter_size && !b.array_offset && !b.num && !b.base_lg);
+    }
+}
+
+struct Span {
+    uint64_t lo, hi;
+};
+
+void fuzz(const uint8_t *image, uint64_t fb, const lv_sst_bloom &sound, const Span spans[3],
+          const std::vector<std::string> &keys, int rounds) {
+    for (int round = 0; round < rounds; ++round) {
+        uint8_t *bad = exact(image, fb);
+        const int flips = round % 2 ? 1 + static_cast<int>(rnd() % 4) : 1;
+        const Span &sp = spans[round % 3];
+        for (int f = 0; f < flips; ++f) bad[sp.lo + rnd() % (sp.hi - sp.lo)] = static_cast<uint8_t>(rnd());
+        const uint64_t cut = round % 16 == 15 ? rnd() % (fb + 1) : fb;  // now and then a truncated file
+        uint8_t *file = cut == fb ? bad : exact(bad, cut);
+        lv_sst_table t;
+        lv_sst_bloom b;
+        CHECK(lv_sst_open_host(file, cut, nullptr, 0, &t) == 0);
+        std::memset(&b, 0xEE, sizeof b);
+        CHECK(lv_sst_bloom_open_host(file, &t, &b) == 0);
+        check_bloom_sane(b, cut);
+        // a table that open did not write for this file: the sound footer's handles over the cut file
+        lv_sst_table forced = t;
+        lv_sst_bloom fb2;
+        if (t.status) {
+            CHECK(lv_sst_open_host(image, fb, nullptr, 0, &forced) == 0);
+            forced.file_bytes = cut;
+        }
+        CHECK(lv_sst_bloom_open_host(file, &forced, &fb2) == 0);
+        check_bloom_sane(fb2, cut);
+        lv_sst_bloom wild = sound;  // not written for this file
+        if (round % 4 == 1) wild.filter_offset = rnd();
+        if (round % 4 == 2) wild.array_offset = rnd() % (2 * sound.filter_size + 1);
+        if (round % 4 == 3) wild.num = rnd(), wild.base_lg = rnd() % 80;
+        for (size_t q = 0; q < 6; ++q) {
+            const std::string &k = keys[rnd() % keys.size()];
+            lv_sst_get_result r, plain;
+            CHECK(get(file, t, &b, k, rnd() % 8, &r) == 0);
+            check_sane(r, cut);
+            const uint64_t seq = rnd() % 8;
+            CHECK(get(file, forced, &fb2, k, seq, &r) == 0);
+            check_sane(r, cut);
+            CHECK(get(file, forced, nullptr, k, seq, &plain) == 0);
+            if (!r.reserved) CHECK(std::memcmp(&r, &plain, sizeof r) == 0);  // a filter only ever turns an answer into FILTERED
+            CHECK(get(file, forced, &wild, k, seq, &r) == 0);
+            check_sane(r, cut);
+            if (!r.reserved) CHECK(std::memcmp(&r, &plain, sizeof r) == 0);
+        }
+        if (file != bad) std::free(file);
+        std::free(bad);
+    }
+}
+
+void check_table(const std::vector<Item> &items, uint32_t bs, uint32_t ri, uint32_t bpk, int fuzz_rounds) {
+    std::string p;
+    std::vector<lv_wb_op> ops;
+    for (const Item &it : items) {
+        lv_wb_op o{};
+        o.tag = it.tag;
+        o.key_off = p.size();
+        o.key_len = static_cast<uint32_t>(it.key.size());
+        p += it.key;
+        o.val_off = p.size();
+        o.val_len = static_cast<uint32_t>(it.value.size());
+        p += it.value;
+        ops.push_back(o);
+    }
+    const size_t n = items.size();
+    uint8_t *payload = exact(p.data(), p.size());
+    std::vector<uint32_t> order(n ? n : 1);
+    lv_mt_totals mt{};
+    CHECK(lv_memtable_build_host(payload, p.size(), n ? ops.data() : nullptr, n, n ? order.data() : nullptr, &mt) == 0);
+    const lv_sst_build_options opt{bs, ri};
+    const lv_sst_bloom_options bopt{bpk, 0};
+    lv_sst_build_totals size{}, tot{}, ptot{};
+    lv_sst_bloom_totals bsize{}, bt{};
+    CHECK(lv_sst_build_bloom_host(payload, p.size(), ops.data(), order.data(), &mt, &opt, &bopt, nullptr, 0, nullptr, 0,
+                                  &size, &bsize) == 0);
+    CHECK(size.file_bytes <= lv_sst_build_bloom_file_bound(p.size(), n, &opt, &bopt));
+    uint8_t *file = static_cast<uint8_t *>(std::malloc(size.file_bytes ? size.file_bytes : 1));
+    uint64_t *built = static_cast<uint64_t *>(std::malloc(16 * (size.data_blocks + 3)));
+    CHECK(lv_sst_build_bloom_host(payload, p.size(), ops.data(), order.data(), &mt, &opt, &bopt,
+                                  size.file_bytes ? file : nullptr, size.file_bytes, built, size.data_blocks, &tot,
+                                  &bt) == 0);
+    CHECK(tot.status == 0 && std::memcmp(&tot, &size, sizeof tot) == 0 && std::memcmp(&bt, &bsize, sizeof bt) == 0);
+    const uint64_t fb = tot.file_bytes;
+    // the data blocks are the plain build's
+    CHECK(lv_sst_build_host(payload, p.size(), ops.data(), order.data(), &mt, &opt, nullptr, 0, nullptr, 0, &ptot) == 0);
+    CHECK(ptot.data_blocks == tot.data_blocks && ptot.entries == tot.entries);
+    if (fb) {
+        uint8_t *plain = static_cast<uint8_t *>(std::malloc(ptot.file_bytes));
+        uint64_t *ph = static_cast<uint64_t *>(std::malloc(16 * (ptot.data_blocks + 2)));
+        CHECK(lv_sst_build_host(payload, p.size(), ops.data(), order.data(), &mt, &opt, plain, ptot.file_bytes, ph,
+                                ptot.data_blocks, &ptot) == 0);
+        CHECK(ptot.metaindex_offset == bt.filter_offset && std::memcmp(plain, file, ptot.metaindex_offset) == 0);
+        CHECK(std::memcmp(ph, built, 16 * ptot.data_blocks) == 0);
+        std::free(ph);
+        std::free(plain);
+    }
+    // the open (no filter policy needed) and the filter
+    uint64_t *handles = static_cast<uint64_t *>(std::malloc(16 * (tot.data_blocks + 2)));
+    lv_sst_table t;
+    lv_sst_bloom b;
+    CHECK(lv_sst_open_host(fb ? file : nullptr, fb, handles, tot.data_blocks, &t) == 0);
+    CHECK(t.status == 0 && t.file_bytes == fb && t.data_blocks == tot.data_blocks);
+    CHECK(t.metaindex_offset == tot.metaindex_offset && t.metaindex_size == tot.metaindex_size);
+    if (fb) {
+        CHECK(std::memcmp(handles, built, 16 * tot.data_blocks) == 0);
+        CHECK(std::memcmp(handles + 2 * tot.data_blocks, built + 2 * tot.data_blocks + 2, 32) == 0);
+    }
+    CHECK(lv_sst_bloom_open_host(fb ? file : nullptr, &t, &b) == 0);
+    check_bloom_sane(b, fb);
+    if (fb) {
+        CHECK(b.present == 1 && b.filter_offset == bt.filter_offset && b.filter_size == bt.filter_size);
+        CHECK(b.num == bt.filters && b.base_lg == LV_SST_FILTER_BASE_LG && bt.filter_keys == n);
+        const uint64_t last = built[2 * (tot.data_blocks - 1)];
+        CHECK(bt.filters == ((last >> 11) + 1 > (bt.filter_offset >> 11) ? (last >> 11) + 1 : bt.filter_offset >> 11));
+    } else {
+        CHECK(b.present == 0 && b.why == LV_SST_BLOOM_EMPTY);
+    }
+    // the gets: lv_sst_get_host's answers
+    std::vector<std::pair<std::string, uint64_t>> qs;
+    std::vector<bool> visible;  // the query sees a stored version of its key
+    std::vector<std::string> keys;
+    for (const Item &it : items) {
+        const uint64_t seq = it.tag >> 8;
+        for (uint64_t s : {seq - 1, seq, seq + 1, uint64_t{0}, uint64_t{LV_MT_MAX_SEQUENCE}})
+            if (s <= LV_MT_MAX_SEQUENCE) {
+                qs.emplace_back(it.key, s);
+                visible.push_back(s >= seq);
+            }
+        keys.push_back(it.key);
+    }
+    for (const Item &it : items) {
+        std::string k = it.key;
+        qs.emplace_back(k + std::string(1, '\0'), LV_MT_MAX_SEQUENCE);
+        if (!k.empty()) {
+            qs.emplace_back(k.substr(0, k.size() - 1), LV_MT_MAX_SEQUENCE);
+            k.back() = static_cast<char>(k.back() + 1);
+            qs.emplace_back(k, LV_MT_MAX_SEQUENCE);
+            k.back() = static_cast<char>(k.back() - 2);
+            qs.emplace_back(k, 3);
+        }
+    }
+    qs.emplace_back("", LV_MT_MAX_SEQUENCE);
+    qs.emplace_back("\xff\xff\xff\xff", 1);
+    keys.push_back("");
+    keys.push_back("absent");
+    for (size_t i = 0; i < qs.size(); ++i) {
+        lv_sst_get_result r, plain;
+        CHECK(get(file, t, &b, qs[i].first, qs[i].second, &r) == 0);
+        CHECK(get(file, t, nullptr, qs[i].first, qs[i].second, &plain) == 0);
+        check_sane(r, fb);
+        if (i < visible.size() && visible[i]) CHECK(r.reserved == 0 && r.status != LV_SST_GET_ABSENT);
+        if (r.reserved)
+            CHECK(plain.status == LV_SST_GET_ABSENT);
+        else
+            CHECK(std::memcmp(&r, &plain, sizeof r) == 0);
+    }
+    lv_sst_get_result r;
+    CHECK(get(file, t, &b, "k", LV_MT_MAX_SEQUENCE + 1, &r) == 0 && r.status == LV_SST_GET_BAD_SEQ);
+    lv_sst_table failed = t;
+    failed.status = LV_SST_OPEN_BAD_INDEX;
+    CHECK(get(file, failed, &b, "k", 1, &r) == 0 && r.status == LV_SST_GET_NO_TABLE && r.tag == 0);
+    lv_sst_bloom none;
+    CHECK(lv_sst_bloom_open_host(file, &failed, &none) == 0 && none.present == 0 && none.why == LV_SST_BLOOM_TABLE);
+    if (fb && fuzz_rounds) {
+        const Span spans[3] = {{bt.filter_offset, bt.filter_offset + bt.filter_size + 5},
+                               {tot.metaindex_offset, tot.metaindex_offset + tot.metaindex_size + 5},
+                               {fb - LV_SST_FOOTER_SIZE, fb}};
+        fuzz(file, fb, b, spans, keys, fuzz_rounds);
+    }
+    std::free(handles);
+    std::free(built);
+    std::free(file);
+    std::free(payload);
+}
+
+std::vector<Item> seq_items(size_t n, size_t vlen = 3) {
+    std::vector<Item> v;
+    for (size_t i = 0; i < n; ++i) {
+        char k[24];
+        std::snprintf(k, sizeof k, "%06zu", i);
+        v.push_back({k, std::string(vlen, 'v'), tag(100 + i, 1)});
+    }
+    return v;
+}
+
+// the host scalars over heap blocks of exactly their size
+void check_scalars() {
+    const uint8_t b = 0x62;
+    uint8_t *k = exact(&b, 1);
+    CHECK(lv_bloom_hash(k, 1) == 0xef1345c4u);
+    std::free(k);
+    for (uint32_t bpk : {1u, 10u, 64u})
+        for (size_t n : {0, 1, 6, 7, 63, 64, 65, 300}) {
+            std::string blob;
+            std::vector<uint64_t> off;
+            std::vector<uint32_t> len;
+            for (size_t i = 0; i < n; ++i) {
+                off.push_back(blob.size());
+                len.push_back(static_cast<uint32_t>(rnd() % 12));
+                for (uint32_t j = 0; j < len.back(); ++j) blob.push_back(static_cast<char>(rnd()));
+            }
+            uint8_t *keys = exact(blob.data(), blob.size());
+            const size_t fbytes = lv_bloom_filter_bytes(n, bpk);
+            uint8_t *f = static_cast<uint8_t *>(std::malloc(fbytes));
+            CHECK(lv_bloom_create_filter(keys, off.data(), len.data(), n, bpk, f) == 0);
+            for (size_t i = 0; i < n; ++i) {
+                uint8_t *one = exact(blob.data() + off[i], len[i]);
+                CHECK(lv_bloom_key_may_match(one, len[i], f, fbytes) == 1);
+                std::free(one);
+            }
+            CHECK(lv_bloom_key_may_match(nullptr, 0, f, 1) == 0 && lv_bloom_key_may_match(nullptr, 0, nullptr, 0) == 0);
+            std::free(f);
+            std::free(keys);
+        }
+}
+
+// ---- the dumped cases (tests/sst_bloom_cases.py dump) ----
+struct In {
+    std::vector<uint8_t> b;
+    size_t at = 0;
+    bool ok = true;
+    uint64_t u64() {
+        uint64_t v = 0;
+        if (at + 8 > b.size()) return ok = false, 0;
+        std::memcpy(&v, b.data() + at, 8);
+        at += 8;
+        return v;
+    }
+    const uint8_t *bytes(size_t n) {
+        if (at + n > b.size()) return ok = false, nullptr;
+        at += n;
+        return b.data() + at - n;
+    }
+};
+
+int replay(const char *path) {
+    In in;
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return std::fprintf(stderr, "cannot open %s\n", path), 1;
+    uint8_t buf[65536];
+    for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) in.b.insert(in.b.end(), buf, buf + n);
+    std::fclose(f);
+    const uint64_t cases = in.u64();
+    uint64_t queries = 0;
+    for (uint64_t c = 0; c < cases && in.ok; ++c) {
+        const uint64_t fb = in.u64();
+        uint8_t *file = exact(in.bytes(fb), fb);
+        lv_sst_bloom want{}, b;
+        std::memcpy(&want, in.bytes(sizeof want), sizeof want);
+        lv_sst_table t;
+        CHECK(lv_sst_open_host(file, fb, nullptr, 0, &t) == 0);
+        CHECK(lv_sst_bloom_open_host(file, &t, &b) == 0);
+        CHECK(std::memcmp(&b, &want, sizeof b) == 0);
+        const uint64_t nq = in.u64();
+        for (uint64_t q = 0; q < nq && in.ok; ++q) {
+            const uint64_t kl = in.u64();
+            const std::string key(reinterpret_cast<const char *>(in.bytes(kl)), kl);
+            const uint64_t seq = in.u64();
+            lv_sst_get_result want_r{}, r;
+            std::memcpy(&want_r, in.bytes(sizeof want_r), sizeof want_r);
+            CHECK(get(file, t, &b, key, seq, &r) == 0);
+            CHECK(std::memcmp(&r, &want_r, sizeof r) == 0);
+            ++queries;
+        }
+        std::free(file);
+    }
+    CHECK(in.ok && in.at == in.b.size());
+    std::printf("sst_bloom_host_check: replayed %llu cases, %llu queries\n", static_cast<unsigned long long>(cases),
+                static_cast<unsigned long long>(queries));
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    check_scalars();
+    for (size_t n : {0, 1, 15, 63, 64, 65}) check_table(seq_items(n), 4096, 16, 10, 40);
+    for (uint32_t bpk : {1u, 10u, 64u}) check_table(seq_items(40), 256, 4, bpk, 300);
+    check_table(seq_items(300, 10), 256, 16, 10, 1500);
+    check_table(seq_items(400, 100), 8192, 16, 10, 300);
+    check_table(seq_items(400, 100), 5000, 16, 10, 300);
+    for (size_t end : {2047, 2048, 2049, 4095, 4096, 4097})
+        check_table({{"k", std::string(end - 26, 'e'), tag(1, 1)}}, 4096, 16, 10, 30);
+    check_table({{"a", std::string(9000, 'B'), tag(1, 1)}, {"b", "s", tag(2, 1)}, {"c", "t", tag(3, 1)}}, 4096, 16, 10, 50);
+    {
+        std::vector<Item> lens;  // user keys of 0 .. 9 bytes
+        for (size_t n = 0; n < 10; ++n) lens.push_back({std::string("ABCDEFGHI", n), "v", tag(n + 1, 1)});
+        check_table(lens, 4096, 16, 10, 50);
+        std::vector<Item> versions;
+        for (uint64_t s = 1; s <= 40; ++s) versions.push_back({"same", "v", tag(s, s % 4 ? 1 : 0)});
+        for (int d = 0; d < 3; ++d) versions.push_back({"same", "v", tag(7, 1)});
+        check_table(versions, 128, 4, 10, 100);
+    }
+    check_table(seq_items(5000, 0), 1u << 30, 16, 10, 100);  // one filter of several KiB
+    // pseudo-random tables over small alphabets and small blocks
+    for (int trial = 0; trial < 200; ++trial) {
+        const unsigned sym = trial % 3 == 0 ? 2 : trial % 3 == 1 ? 4 : 256;
+        const size_t n = rnd() % 150;
+        std::vector<Item> items;
+        for (size_t i = 0; i < n; ++i) {
+            std::string k(rnd() % (trial % 2 ? 24 : 7), '\0');
+            for (char &c : k) c = static_cast<char>(sym == 256 ? 250 + rnd() % 6 : rnd() % sym);
+            const uint32_t type = rnd() % 4 ? 1 : 0;
+            items.push_back({k, type ? std::string(rnd() % 40, 'v') : "", tag(rnd() % 6, type)});
+        }
+        const uint32_t bss[] = {1, 32, 64, 300, 4096};
+        const uint32_t ris[] = {1, 2, 4, 16, 1024};
+        const uint32_t bpks[] = {1, 5, 10, 64};
+        check_table(items, bss[trial % 5], ris[(trial / 5) % 5], bpks[trial % 4], 15);
+    }
+    if (argc > 1 && replay(argv[1])) return 1;
+    if (g_fail) {
+        std::fprintf(stderr, "sst_bloom_host_check: %d check(s) failed\n", g_fail);
+        return 1;
+    }
+    std::puts("sst_bloom_host_check: ok");
+    return 0;
+}
