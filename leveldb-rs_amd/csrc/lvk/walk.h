@@ -162,7 +162,12 @@ __device__ __forceinline__ uint32_t fold_tail(uint32_t X, uint4 V, const RGeo &q
     const uint32_t k = end & 15u;
     if (k == 0) return X;
     const uint32_t s0 = q.len >= 4 ? ~q.seed : 0u;
-    const int32_t rel = static_cast<int32_t>(end & ~15u) - static_cast<int32_t>(alow);
+    // the tail granule's position from the buffer start.  fix_word tells
+    // positions apart only below 16, so a longer distance is held at 16: as
+    // an int32 it wrapped for buffers of 2^31 bytes and more, and the tail
+    // was zeroed as if it lay before the buffer.
+    const uint32_t whole = end & ~15u;
+    const int32_t rel = whole >= 16u + alow ? 16 : static_cast<int32_t>(whole) - static_cast<int32_t>(alow);
     uint32_t w[4] = {fix_word(V.x, rel, s0), fix_word(V.y, rel + 4, s0), fix_word(V.z, rel + 8, s0),
                      fix_word(V.w, rel + 12, s0)};
 #pragma unroll

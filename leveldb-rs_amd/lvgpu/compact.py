@@ -160,7 +160,10 @@ def filter_device(table, snapshot, ranges=None, flags=0, *, op_cap=None, order_t
     Scanned.memtable() or an earlier Filtered): its payload, ops, order and
     totals, read on the device.  ranges is a list of (lo, hi) byte strings (or
     pack_ranges' pair), copied to the device here.  order_t / mt_totals / totals
-    reuse the outputs of an earlier call (graph replays).  fill, a byte value,
+    reuse the outputs of an earlier call (graph replays).  ranges may also be
+    (RANGE_DTYPE array, uint8 CUDA tensor): range keys that already lie in HBM,
+    the rows' offsets pointing into that tensor, which is passed as it is
+    (range_key_bytes = its numel(): offsets beyond 4 GiB).  fill, a byte value,
     initialises d_order_out with it first and guard allocates that many more
     bytes behind it (canaries).  Returns a Filtered; asynchronous on `stream`."""
     import torch
@@ -168,12 +171,19 @@ def filter_device(table, snapshot, ranges=None, flags=0, *, op_cap=None, order_t
     L = _bind()
     dev = table.payload.device
     op_cap = int(table.op_cap) if op_cap is None else int(op_cap)
-    rr, rk = _ranges(ranges)
     d_rr = d_rk = None
+    if isinstance(ranges, tuple) and len(ranges) == 2 and torch.is_tensor(ranges[1]):
+        rr, d_rk = np.ascontiguousarray(ranges[0], dtype=RANGE_DTYPE), ranges[1]
+        if d_rk.dtype != torch.uint8 or d_rk.device != dev:
+            raise LvError("range keys must be a uint8 tensor on the payload's device")
+        rk_bytes = d_rk.numel()
+    else:
+        rr, rk = _ranges(ranges)
+        rk_bytes = len(rk)
+        if rk:
+            d_rk = torch.frombuffer(bytearray(rk), dtype=torch.uint8).to(dev)
     if rr.size:
         d_rr = torch.from_numpy(np.frombuffer(rr.tobytes(), dtype=np.int64).copy()).to(dev)
-    if rk:
-        d_rk = torch.frombuffer(bytearray(rk), dtype=torch.uint8).to(dev)
     if workspace is None:
         workspace = torch.empty(max(L.lv_compact_filter_workspace_bytes(op_cap), 16), dtype=torch.uint8, device=dev)
     if order_t is None:
@@ -191,7 +201,7 @@ def filter_device(table, snapshot, ranges=None, flags=0, *, op_cap=None, order_t
                                         table.payload.numel(), _dev_ptr(table.ops_t, "ops") if op_cap else None,
                                         _dev_ptr(table.order_t, "order") if op_cap else None,
                                         _dev_ptr(table.totals, "mt_totals"), op_cap, snapshot,
-                                        _dev_ptr(d_rr, "ranges"), rr.size, _dev_ptr(d_rk, "range_keys"), len(rk),
+                                        _dev_ptr(d_rr, "ranges"), rr.size, _dev_ptr(d_rk, "range_keys"), rk_bytes,
                                         _dev_ptr(order_t, "order_out") if op_cap else None,
                                         _dev_ptr(mt_totals, "mt_totals_out"), _dev_ptr(totals, "totals"), flags,
                                         _dev_ptr(workspace, "workspace"), workspace.numel(), _stream_ptr(stream))
