@@ -195,6 +195,27 @@ const char *lv_crc32c_last_kernel(void);
  * buffers and that cached host paths stop allocating.  0 or LV_ERR_INVALID. */
 int lv_device_counters(int device, uint64_t *out, size_t n);
 
+/* Debug query: the grid (workgroups) the library launches `kernel` on for
+ * `units` of work on a device with `cus` compute units, and in
+ * *units_per_workgroup_trip (may be NULL) the units one workgroup consumes in
+ * one trip of its grid-stride loop -- the launchers' own arithmetic, no device
+ * is asked.  A workgroup goes round its loop ceil(ceil(units / per trip) /
+ * grid) times.  Units by kernel: hash_kernel keys; wb_count, wb_emit, wb_tiles
+ * records (rec_cap); wal_frame_kernel, wal_unframe_kernel log blocks;
+ * wal_dec_classify, wal_dec_reduce, wal_dec_apply, wal_dec_tiles, wal_unsort
+ * scan entries (scan_cap); sb_bloom_emit, sb_bloom_big data blocks (op_cap);
+ * sb_bloom_offsets filter windows (file_cap >> 11); so_validate data blocks
+ * (block_cap); so_emit handles (block_cap + 2); ss_count restart runs
+ * (op_cap + block_cap); sst_blocks_kernel and combine_pieces_kernel blocks.
+ * The one-workgroup round
+ * loops (wb_tiles, wal_dec_tiles; sb_carry, ss_carry and cf_carry, in entries
+ * or data blocks) report grid 1 and the units of a round.
+ * Returns 0 for an unknown name, no work or cus <= 0.  Lets tests size their
+ * inputs so that a workgroup takes a second and a third trip. */
+uint64_t lv_debug_launch_grid(const char *kernel, uint64_t units, int cus, uint64_t *units_per_workgroup_trip);
+/* The kernel names lv_debug_launch_grid knows, separated by spaces. */
+const char *lv_debug_launch_grid_names(void);
+
 /* ---- page-locked host memory for callers' file buffers ------------------- */
 
 /* Page-locked (pinned) host memory: a caller that reads a log or table file

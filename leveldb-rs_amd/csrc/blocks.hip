@@ -376,6 +376,12 @@ __global__ __launch_bounds__(1024) void combine_pieces_wg_kernel(const uint32_t 
 
 }  // namespace lvk
 
+// combine_pieces_kernel: a wave per split block, 4 blocks a workgroup trip.
+uint64_t lvgpu_internal::combine_pieces_grid(uint64_t blocks, uint64_t *per_trip) {
+    if (per_trip) *per_trip = 4;
+    return std::min<uint64_t>(1024, (blocks + 3) / 4);
+}
+
 namespace lvh {
 
 template <int G, bool STRIDED>
@@ -549,7 +555,7 @@ void launch_pieces(DevCtx &c, uint32_t ps, const uint32_t *mats, const uint32_t 
         g_kernel = GATHER ? "crc32c_blocks_kernel<16,pieces,gather>+combine_pieces_wg_kernel"
                           : "crc32c_blocks_kernel<16,pieces>+combine_pieces_wg_kernel";
     } else {
-        hipLaunchKernelGGL(lvk::combine_pieces_kernel, dim3(static_cast<uint32_t>(std::min<uint64_t>(1024, (n + 3) / 4))),
+        hipLaunchKernelGGL(lvk::combine_pieces_kernel, dim3(static_cast<uint32_t>(lvgpu_internal::combine_pieces_grid(n))),
                            dim3(256), 0, hs, P.out, n, 1u << ps, mats, out, flags);
         g_kernel = GATHER ? "crc32c_blocks_kernel<16,pieces,gather>+combine_pieces_kernel"
                           : "crc32c_blocks_kernel<16,pieces>+combine_pieces_kernel";

@@ -260,6 +260,9 @@ uint64_t cf_carve(Carve &C, uint64_t cap, lvk::CfArgs &A) {
 
 }  // namespace
 
+// cf_carry scans 64 tile sums a round (lvk::carry_scan).
+uint64_t lvgpu_internal::cf_carry_round() { return 64ull * lvk::kCfTile; }
+
 extern "C" {
 
 size_t lv_compact_filter_workspace_bytes(size_t op_cap) {

@@ -387,6 +387,62 @@ int lv_device_counters(int device, uint64_t *out, size_t n) {
     return LV_OK;
 }
 
+uint64_t lv_debug_launch_grid(const char *kernel, uint64_t units, int cus, uint64_t *units_per_workgroup_trip) {
+    namespace li = lvgpu_internal;
+    if (!kernel || cus <= 0) return 0;
+    const std::string k(kernel);
+    const uint64_t c = static_cast<uint64_t>(cus);
+    uint64_t per = 0, grid = 0;
+    if (k == "hash_kernel")
+        grid = li::hash_grid(units, c, &per);
+    else if (k == "wb_count" || k == "wb_emit")
+        grid = li::wb_grid(units, c, &per);
+    else if (k == "wb_tiles")
+        grid = units ? 1 : 0, per = li::wb_tiles_round();
+    else if (k == "wal_frame_kernel")
+        grid = li::wal_frame_grid(units, c, &per);
+    else if (k == "wal_unframe_kernel")
+        grid = li::wal_unframe_grid(units, c, &per);
+    else if (k == "wal_dec_classify")
+        grid = li::wal_classify_grid(units, c, &per);
+    else if (k == "wal_dec_reduce" || k == "wal_dec_apply")
+        grid = li::wal_tile_grid(units, c, &per);
+    else if (k == "wal_dec_tiles")
+        grid = units ? 1 : 0, per = li::wal_dec_tiles_round();
+    else if (k == "sb_carry")
+        grid = units ? 1 : 0, per = li::sb_carry_round();
+    else if (k == "ss_carry")
+        grid = units ? 1 : 0, per = li::ss_carry_round();
+    else if (k == "cf_carry")
+        grid = units ? 1 : 0, per = li::cf_carry_round();
+    else if (k == "wal_unsort")
+        grid = li::wal_unsort_grid(units, c, &per);
+    else if (k == "sb_bloom_emit" || k == "sb_bloom_big")
+        grid = li::sb_bloom_grid(units, &per);
+    else if (k == "sb_bloom_offsets")
+        grid = li::sb_bloom_offsets_grid(units, &per);
+    else if (k == "so_validate")  // walks the data blocks on the grid of block_cap + 2 lanes
+        grid = li::so_grid(units + 2, &per);
+    else if (k == "so_emit")
+        grid = li::so_grid(units, &per);
+    else if (k == "ss_count")
+        grid = li::ss_count_grid(units, &per);
+    else if (k == "sst_blocks_kernel")
+        grid = li::sst_blocks_grid(units, c, &per);
+    else if (k == "combine_pieces_kernel")
+        grid = li::combine_pieces_grid(units, &per);
+    else
+        return 0;
+    if (units_per_workgroup_trip) *units_per_workgroup_trip = per;
+    return grid;
+}
+
+const char *lv_debug_launch_grid_names(void) {
+    return "hash_kernel wb_count wb_emit wb_tiles wal_frame_kernel wal_unframe_kernel wal_dec_classify wal_dec_reduce "
+           "wal_dec_apply wal_dec_tiles wal_unsort sb_bloom_emit sb_bloom_big sb_bloom_offsets so_validate so_emit "
+           "ss_count sst_blocks_kernel sb_carry ss_carry cf_carry combine_pieces_kernel";
+}
+
 void *lv_host_alloc(size_t bytes) {
     g_err.clear();
     void *p = nullptr;

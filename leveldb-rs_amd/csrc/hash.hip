@@ -56,6 +56,7 @@
 // 0.87 GB -- runs at 0.77 of 8 TB/s: HBM binds.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstring>
 
@@ -399,11 +400,16 @@ uint32_t hash_grid(size_t n) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
         if (dev >= 0 && dev < 64) cus_cache[dev].store(cus, std::memory_order_relaxed);
     }
-    const uint64_t want = (n + 255) / 256, cap = static_cast<uint64_t>(cus) * kWgsPerCu;
-    return static_cast<uint32_t>(want < cap ? want : cap);
+    return static_cast<uint32_t>(lvgpu_internal::hash_grid(n, static_cast<uint64_t>(cus)));
 }
 
 }  // namespace lvh
+
+// hash_kernel's grid for n keys: a workgroup takes 256 keys (a wave 64) a trip.
+uint64_t lvgpu_internal::hash_grid(uint64_t n, uint64_t cus, uint64_t *per_trip) {
+    if (per_trip) *per_trip = 256;
+    return std::min<uint64_t>((n + 255) / 256, cus * lvh::kWgsPerCu);
+}
 
 extern "C" {
 

@@ -124,4 +124,32 @@ void count_h2d(uint64_t bytes);
 void count_d2h(uint64_t bytes);
 // ... and an allocation the host path made for `device` (any thread).
 void count_alloc(int device);
+
+// ---- grids of the capped kernels ----
+// A kernel whose grid is capped walks the rest of its work in a grid-stride
+// loop.  Each launcher takes its grid from one of these (pure arithmetic:
+// work size and compute units in, workgroups out; *per_trip, when asked for,
+// is the units one workgroup consumes in one trip of its loop), and
+// lv_debug_launch_grid hands the same functions to the tests, which size
+// their inputs for a second and third trip from them.
+uint64_t hash_grid(uint64_t keys, uint64_t cus, uint64_t *per_trip = nullptr);              // hash_kernel
+uint64_t wb_grid(uint64_t rec_cap, uint64_t cus, uint64_t *per_trip = nullptr);             // wb_count, wb_emit
+uint64_t wal_frame_grid(uint64_t blocks, uint64_t cus, uint64_t *per_trip = nullptr);       // wal_frame_kernel
+uint64_t wal_unframe_grid(uint64_t blocks, uint64_t cus, uint64_t *per_trip = nullptr);     // wal_unframe_kernel
+uint64_t wal_classify_grid(uint64_t scan_cap, uint64_t cus, uint64_t *per_trip = nullptr);  // wal_dec_classify
+uint64_t wal_tile_grid(uint64_t scan_cap, uint64_t cus, uint64_t *per_trip = nullptr);      // wal_dec_reduce, wal_dec_apply
+uint64_t wal_unsort_grid(uint64_t cap, uint64_t cus, uint64_t *per_trip = nullptr);         // wal_unsort
+uint64_t sb_bloom_grid(uint64_t op_cap, uint64_t *per_trip = nullptr);          // sb_bloom_emit, sb_bloom_big (blocks <= op_cap)
+uint64_t sb_bloom_offsets_grid(uint64_t windows, uint64_t *per_trip = nullptr); // sb_bloom_offsets (file_cap >> 11 windows)
+uint64_t so_grid(uint64_t lanes, uint64_t *per_trip = nullptr);                 // so_validate, so_emit (block_cap + 2 lanes)
+uint64_t ss_count_grid(uint64_t runs, uint64_t *per_trip = nullptr);            // ss_count (restart runs, <= run_cap)
+uint64_t sst_blocks_grid(uint64_t blocks, uint64_t cus, uint64_t *per_trip = nullptr);      // sst_blocks_kernel (wave claims)
+uint64_t combine_pieces_grid(uint64_t blocks, uint64_t *per_trip = nullptr);                // combine_pieces_kernel
+// The one-workgroup round loops: entries a round takes (the grid is 1).
+uint64_t wb_tiles_round();       // wb_tiles: records per round
+uint64_t wal_dec_tiles_round();  // wal_dec_tiles: scan entries per round
+// The carry kernels: one wave scans a column of tile totals 64 tiles a round (lvk::carry_scan).
+uint64_t sb_carry_round();  // sb_carry: entries (the filters' column: data blocks) per round
+uint64_t ss_carry_round();  // ss_carry: data blocks, and restart runs, per round
+uint64_t cf_carry_round();  // cf_carry: entries per round
 }

@@ -201,6 +201,14 @@ __global__ __launch_bounds__(kThreads) void sst_blocks_kernel(Params P, const ui
 
 namespace lvgpu_internal {
 using namespace lvh;
+constexpr uint64_t kRunUnits = 4ull * lvk::kSstRun;  // blocks per wave claim
+// sst_blocks_kernel: the waves of a workgroup claim runs of kRunUnits blocks
+// from the workgroup's pool; claim k of workgroup b is run b + grid * k, so a
+// workgroup's second claim is its second trip.
+uint64_t sst_blocks_grid(uint64_t blocks, uint64_t cus, uint64_t *per_trip) {
+    if (per_trip) *per_trip = kRunUnits;
+    return std::min<uint64_t>(cus, (blocks + kRunUnits - 1) / kRunUnits);
+}
 // SSTable trailers (csrc/sst.hip): one sst_blocks_kernel launch.
 int launch_sst_blocks(bool seal, const uint8_t *d_file, uint64_t file_bytes, const uint64_t *d_handles,
                       const uint8_t *d_types, size_t n, uint32_t *d_status, uint32_t *d_crc, void *stream) {
@@ -208,12 +216,11 @@ int launch_sst_blocks(bool seal, const uint8_t *d_file, uint64_t file_bytes, con
     if (int rc = current_ctx(&c)) return rc;
     lvk::Params P{};
     P.base = reinterpret_cast<uint64_t>(d_file);
-    constexpr uint64_t kRunUnits = 4ull * lvk::kSstRun;  // blocks per wave claim
     const uint64_t claims = (n + kRunUnits - 1) / kRunUnits;
     P.n = claims * kRunUnits;  // entries of the walk; those past the last block are empty lanes
     P.flags = 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>(c->cus, claims))), block(lvk::kThreads);
+    const dim3 grid(static_cast<uint32_t>(sst_blocks_grid(n, static_cast<uint64_t>(c->cus)))), block(lvk::kThreads);
     if (seal) {
         lvk::TableUnits<true> u{reinterpret_cast<const uint2 *>(d_handles), d_types, nullptr, nullptr, file_bytes, n};
         g_kernel = "sst_blocks_kernel<seal>";

@@ -938,6 +938,21 @@ int sb_build(const uint8_t *d_payload, size_t payload_bytes, const lv_wb_op *d_o
 
 }  // namespace
 
+// sb_bloom_emit / sb_bloom_big: a wave per data block, so a workgroup takes
+// kSbThreads / 64 blocks a trip; the table has at most op_cap blocks.
+uint64_t lvgpu_internal::sb_bloom_grid(uint64_t op_cap, uint64_t *per_trip) {
+    constexpr uint64_t kWaves = lvk::kSbThreads / 64;
+    if (per_trip) *per_trip = kWaves;
+    return std::min<uint64_t>((op_cap + kWaves - 1) / kWaves, 1024);
+}
+// sb_carry scans 64 tile sums a round (lvk::carry_scan).
+uint64_t lvgpu_internal::sb_carry_round() { return 64ull * lvk::kSbTile; }
+// sb_bloom_offsets: a lane per filter window, kSbThreads windows a workgroup trip.
+uint64_t lvgpu_internal::sb_bloom_offsets_grid(uint64_t windows, uint64_t *per_trip) {
+    if (per_trip) *per_trip = lvk::kSbThreads;
+    return std::min<uint64_t>(windows / lvk::kSbThreads + 1, 1024);
+}
+
 extern "C" {
 
 size_t lv_sst_build_workspace_bytes(size_t op_cap, size_t block_cap) {
@@ -1076,9 +1091,8 @@ int sb_build(const uint8_t *d_payload, size_t payload_bytes, const lv_wb_op *d_o
     if (tiles) hipLaunchKernelGGL(lvk::sb_emit, dim3(eg), b, 0, s, A);
     if (tiles && bloom) {
         // a wave per data block, a lane per window: grid-stride loops over capped grids
-        const uint32_t wg = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(op_cap) + kWaves - 1) / kWaves, 1024));
-        const uint32_t og = static_cast<uint32_t>(
-            std::min<uint64_t>((file_cap >> LV_SST_FILTER_BASE_LG) / lvk::kSbThreads + 1, 1024));
+        const uint32_t wg = static_cast<uint32_t>(lvgpu_internal::sb_bloom_grid(op_cap));
+        const uint32_t og = static_cast<uint32_t>(lvgpu_internal::sb_bloom_offsets_grid(file_cap >> LV_SST_FILTER_BASE_LG));
         hipLaunchKernelGGL(lvk::sb_bloom_emit, dim3(wg), b, 0, s, A);
         hipLaunchKernelGGL(lvk::sb_bloom_big, dim3(wg), b, 0, s, A);
         hipLaunchKernelGGL(lvk::sb_bloom_offsets, dim3(og), b, 0, s, A);

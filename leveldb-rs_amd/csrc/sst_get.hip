@@ -169,6 +169,12 @@ constexpr uint64_t kMaxBlockCap = 0xfffffffcull;
 
 }  // namespace
 
+// so_validate / so_emit: a lane per restart array or handle, kSgThreads a workgroup trip.
+uint64_t lvgpu_internal::so_grid(uint64_t lanes, uint64_t *per_trip) {
+    if (per_trip) *per_trip = lvk::kSgThreads;
+    return std::min<uint64_t>((lanes + lvk::kSgThreads - 1) / lvk::kSgThreads, lvk::kSoMaxGrid);
+}
+
 extern "C" {
 
 int lv_sst_open_device(const uint8_t *d_file, uint64_t file_cap, const uint64_t *d_file_bytes,
@@ -200,8 +206,7 @@ int lv_sst_open_device(const uint8_t *d_file, uint64_t file_cap, const uint64_t 
     A.table = d_table;
     // a lane per restart the caller expects; with no handle array, per 4 KiB of the buffer
     const uint64_t lanes = (block_cap ? static_cast<uint64_t>(block_cap) : file_cap / LV_SST_DEFAULT_BLOCK_SIZE) + 2;
-    const uint32_t grid = static_cast<uint32_t>(
-        std::min<uint64_t>((lanes + lvk::kSgThreads - 1) / lvk::kSgThreads, lvk::kSoMaxGrid));
+    const uint32_t grid = static_cast<uint32_t>(lvgpu_internal::so_grid(lanes));
     hipLaunchKernelGGL(lvk::so_header, dim3(1), dim3(1), 0, s, A);
     hipLaunchKernelGGL(lvk::so_validate, dim3(grid), dim3(lvk::kSgThreads), 0, s, A);
     if (d_handles) hipLaunchKernelGGL(lvk::so_emit, dim3(grid), dim3(lvk::kSgThreads), 0, s, A);

@@ -379,6 +379,15 @@ uint64_t ss_carve(Carve &C, uint64_t op_cap, uint64_t bc, lvk::SsArgs &A) {
 
 }  // namespace
 
+// ss_count: a workgroup takes a tile of kSsTile restart runs a trip (runs <= run_cap = op_cap + block_cap).
+uint64_t lvgpu_internal::ss_count_grid(uint64_t runs, uint64_t *per_trip) {
+    if (per_trip) *per_trip = lvk::kSsTile;
+    return std::min<uint64_t>((runs + lvk::kSsTile - 1) / lvk::kSsTile, lvk::kSsMaxGrid);
+}
+
+// ss_carry scans 64 tile sums a round (lvk::carry_scan).
+uint64_t lvgpu_internal::ss_carry_round() { return 64ull * lvk::kSsTile; }
+
 extern "C" {
 
 size_t lv_sst_scan_workspace_bytes(size_t op_cap, size_t block_cap) {
@@ -452,8 +461,7 @@ int lv_sst_scan_device(const uint8_t *d_file, uint64_t file_cap, const lv_sst_ta
     if (block_cap) {  // (no block: a table with entries is BLOCK_OVER)
         hipLaunchKernelGGL(lvk::ss_blocks, dim3(static_cast<uint32_t>(btiles)), b, 0, s, A);
         hipLaunchKernelGGL(lvk::ss_carry, dim3(1), b, 0, s, A, 0u);
-        hipLaunchKernelGGL(lvk::ss_count, dim3(static_cast<uint32_t>(std::min<uint64_t>(A.run_tiles, lvk::kSsMaxGrid))), b, 0,
-                           s, A);
+        hipLaunchKernelGGL(lvk::ss_count, dim3(static_cast<uint32_t>(lvgpu_internal::ss_count_grid(A.run_cap))), b, 0, s, A);
         hipLaunchKernelGGL(lvk::ss_carry, dim3(1), b, 0, s, A, 1u);
     }
     hipLaunchKernelGGL(lvk::ss_plan, dim3(1), dim3(1), 0, s, A);

@@ -678,6 +678,24 @@ uint64_t dec_carve(Carve &C, uint64_t cap, lvk::DecArgs &A) {
 
 }  // namespace
 
+// wal_dec_classify: a workgroup takes kDecThreads scan entries a trip.
+uint64_t lvgpu_internal::wal_classify_grid(uint64_t scan_cap, uint64_t cus, uint64_t *per_trip) {
+    if (per_trip) *per_trip = lvk::kDecThreads;
+    return std::min<uint64_t>((scan_cap + lvk::kDecThreads - 1) / lvk::kDecThreads, 16 * cus);
+}
+// wal_dec_reduce / wal_dec_apply: a workgroup takes a tile of kDecTile entries a trip.
+uint64_t lvgpu_internal::wal_tile_grid(uint64_t scan_cap, uint64_t cus, uint64_t *per_trip) {
+    if (per_trip) *per_trip = lvk::kDecTile;
+    return std::min<uint64_t>((scan_cap + lvk::kDecTile - 1) / lvk::kDecTile, 8 * cus);
+}
+// wal_unframe_kernel: a workgroup takes one log block a trip (blocks = min(the log's, scan_cap + 1)).
+uint64_t lvgpu_internal::wal_unframe_grid(uint64_t blocks, uint64_t cus, uint64_t *per_trip) {
+    if (per_trip) *per_trip = 1;
+    return std::min<uint64_t>(blocks, 8 * cus);
+}
+// wal_dec_tiles scans kDecThreads tile summaries a round.
+uint64_t lvgpu_internal::wal_dec_tiles_round() { return static_cast<uint64_t>(lvk::kDecThreads) * lvk::kDecTile; }
+
 extern "C" {
 
 size_t lv_wal_decode_workspace_bytes(size_t scan_cap) {
@@ -715,7 +733,7 @@ int lv_wal_decode_device(const uint8_t *d_log, size_t bytes, const uint64_t *d_h
     if (misaligned(d_workspace, 16)) return set_err(LV_ERR_INVALID, "workspace must be 16-byte aligned");
     lvk::DecArgs A{};
     Carve C{static_cast<uint8_t *>(d_workspace)};
-    const uint64_t tiles = dec_carve(C, scan_cap, A);
+    dec_carve(C, scan_cap, A);
     if (workspace_bytes < C.at) return set_err(LV_ERR_INVALID, "workspace too small");
     if (overlaps(out->d_payload, out->payload_cap, d_log, bytes))
         return set_err(LV_ERR_INVALID, "d_payload overlaps d_log");
@@ -738,16 +756,16 @@ int lv_wal_decode_device(const uint8_t *d_log, size_t bytes, const uint64_t *d_h
     const dim3 b(lvk::kDecThreads);
     if (scan_cap) {
         LV_HIP(hipMemsetAsync(A.fkill, 0xff, 3 * A.nb * sizeof(uint32_t), s));
-        const uint64_t g1 = std::min<uint64_t>((scan_cap + lvk::kDecThreads - 1) / lvk::kDecThreads, 16 * cus);
+        const uint64_t g1 = lvgpu_internal::wal_classify_grid(scan_cap, cus);
         hipLaunchKernelGGL(lvk::wal_dec_classify, dim3(static_cast<uint32_t>(g1)), b, 0, s, A);
-        const uint64_t g2 = std::min<uint64_t>(tiles, 8 * cus);
+        const uint64_t g2 = lvgpu_internal::wal_tile_grid(scan_cap, cus);
         hipLaunchKernelGGL(lvk::wal_dec_reduce, dim3(static_cast<uint32_t>(g2)), b, 0, s, A);
     }
     hipLaunchKernelGGL(lvk::wal_dec_tiles, dim3(1), b, 0, s, A);
     if (scan_cap) {
-        const uint64_t g4 = std::min<uint64_t>(tiles, 8 * cus);
+        const uint64_t g4 = lvgpu_internal::wal_tile_grid(scan_cap, cus);
         hipLaunchKernelGGL(lvk::wal_dec_apply, dim3(static_cast<uint32_t>(g4)), b, 0, s, A);
-        const uint64_t g5 = std::min<uint64_t>(std::min<uint64_t>(A.nblocks, A.nb), 8 * cus);
+        const uint64_t g5 = lvgpu_internal::wal_unframe_grid(std::min<uint64_t>(A.nblocks, A.nb), cus);
         if (g5) hipLaunchKernelGGL(lvk::wal_unframe_kernel, dim3(static_cast<uint32_t>(g5)), b, 0, s, A);
     }
     g_kernel = "wal_dec_classify+wal_dec_reduce+wal_dec_tiles+wal_dec_apply+wal_unframe_kernel";

@@ -211,6 +211,12 @@ int stage_acquire(int dev, size_t need, size_t *slot) {
 
 }  // namespace
 
+// wal_frame_kernel: a workgroup takes one 32 KiB log block a trip.
+uint64_t lvgpu_internal::wal_frame_grid(uint64_t blocks, uint64_t cus, uint64_t *per_trip) {
+    if (per_trip) *per_trip = 1;
+    return std::min<uint64_t>(blocks, 8 * cus);
+}
+
 extern "C" {
 
 size_t lv_wal_encode_workspace_bytes(size_t fragments) {
@@ -316,7 +322,7 @@ int lv_wal_encode_device(const uint8_t *d_payload, uint64_t payload_bytes, const
     A.len = D.len;
     A.crc = D.crc;
     A.bidx = D.bidx;
-    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(A.nblocks, 8ull * static_cast<uint64_t>(c->cus)));
+    const uint32_t grid = static_cast<uint32_t>(lvgpu_internal::wal_frame_grid(A.nblocks, static_cast<uint64_t>(c->cus)));
     hipLaunchKernelGGL(lvk::wal_frame_kernel, dim3(grid), dim3(lvk::kFrameThreads), 0, s, A);
     return check_launch();
 }

@@ -371,6 +371,12 @@ __global__ __launch_bounds__(1024) void wal_unsort(const uint32_t *__restrict__ 
 
 using namespace lvh;
 
+// wal_unsort: a workgroup takes 1,024 scan entries a trip.
+uint64_t lvgpu_internal::wal_unsort_grid(uint64_t cap, uint64_t cus, uint64_t *per_trip) {
+    if (per_trip) *per_trip = 1024;
+    return std::min<uint64_t>(cus, (cap + 1023) / 1024);
+}
+
 extern "C" {
 
 // ---- WAL scan of a log in HBM (include/lvgpu/wal.h) ----
@@ -466,7 +472,8 @@ int lv_wal_scan_device(const uint8_t *d_log, size_t bytes, uint64_t *d_hdr_off, 
     launch_classes(*c, false, P, W.ws, s);
     g_kernel = "wal_hist+sort_scan+wal_scatter+crc32c_classes_kernel";
     if (W.tmp && cap) {
-        hipLaunchKernelGGL(lvk::wal_unsort, dim3(static_cast<uint32_t>(std::min<uint64_t>(c->cus, (cap + 1023) / 1024))),
+        hipLaunchKernelGGL(lvk::wal_unsort,
+                           dim3(static_cast<uint32_t>(lvgpu_internal::wal_unsort_grid(cap, static_cast<uint64_t>(c->cus)))),
                            dim3(1024), 0, s, W.ws, W.tmp, W.spos, d_crc, static_cast<uint64_t>(cap));
         g_kernel = "wal_hist+sort_scan+wal_scatter+crc32c_classes_kernel+wal_unsort";
     }

@@ -529,6 +529,14 @@ void wb_carve(Carve &C, uint64_t cap, lvk::WbArgs &A) {
 
 }  // namespace
 
+// wb_count / wb_emit: a workgroup takes a tile of kWbTile records a trip.
+uint64_t lvgpu_internal::wb_grid(uint64_t rec_cap, uint64_t cus, uint64_t *per_trip) {
+    if (per_trip) *per_trip = lvk::kWbTile;
+    return std::min<uint64_t>(wb_tiles_of(rec_cap), 16 * cus);
+}
+// wb_tiles scans kWbScanThreads tile counts a round.
+uint64_t lvgpu_internal::wb_tiles_round() { return static_cast<uint64_t>(lvk::kWbScanThreads) * lvk::kWbTile; }
+
 extern "C" {
 
 size_t lv_write_batch_decode_workspace_bytes(size_t rec_cap) {
@@ -580,7 +588,7 @@ int lv_write_batch_decode_device(const uint8_t *d_payload, size_t payload_bytes,
 
     const uint64_t cus = static_cast<uint64_t>(c->cus > 0 ? c->cus : 1);
     const dim3 b(lvk::kWbThreads);
-    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(wb_tiles_of(rec_cap), 16 * cus));
+    const uint32_t grid = static_cast<uint32_t>(lvgpu_internal::wb_grid(rec_cap, cus));
     LV_HIP(hipMemsetAsync(A.head, 0, sizeof(lvk::WbHead), s));
     if (grid) hipLaunchKernelGGL(lvk::wb_count, dim3(grid), b, 0, s, A);
     hipLaunchKernelGGL(lvk::wb_tiles, dim3(1), dim3(lvk::kWbScanThreads), 0, s, A);

@@ -118,6 +118,10 @@ def lib() -> ctypes.CDLL:
     L.lv_crc32c_last_kernel.argtypes = []
     L.lv_device_counters.restype = ctypes.c_int
     L.lv_device_counters.argtypes = [ctypes.c_int, vp, sz]
+    L.lv_debug_launch_grid.restype = u64
+    L.lv_debug_launch_grid.argtypes = [u8p, u64, ctypes.c_int, vp]
+    L.lv_debug_launch_grid_names.restype = ctypes.c_char_p
+    L.lv_debug_launch_grid_names.argtypes = []
     L.lv_fill_splitmix.restype = ctypes.c_int
     L.lv_fill_splitmix.argtypes = [vp, u64, u64, u64, vp]
     L.lv_host_alloc.restype = vp
@@ -409,3 +413,18 @@ def device_counters(device: int = 0) -> dict:
     v = (ctypes.c_uint64 * 3)()
     _check(lib().lv_device_counters(device, ctypes.cast(v, ctypes.c_void_p), 3))
     return {"h2d": int(v[0]), "d2h": int(v[1]), "allocs": int(v[2])}
+
+
+def launch_grid(kernel: str, units: int, cus: int):
+    """(grid, units one workgroup takes per trip of its grid-stride loop) of a
+    capped kernel for `units` of work on `cus` compute units
+    (lv_debug_launch_grid; host arithmetic, no device); (0, 0) for a name the
+    library does not know."""
+    per = ctypes.c_uint64(0)
+    g = lib().lv_debug_launch_grid(kernel.encode(), int(units), int(cus), ctypes.addressof(per))
+    return int(g), int(per.value)
+
+
+def launch_grid_names() -> list:
+    """The kernel names launch_grid knows."""
+    return lib().lv_debug_launch_grid_names().decode().split()

@@ -145,9 +145,16 @@ def test_second_round_of_tile_scan(gpu):
 
 
 def test_more_blocks_than_compute_units(gpu):
+    """More log blocks than wal_unframe_kernel has workgroups: sized from the
+    launcher's cap (tests/loop_trips.py), so every workgroup takes a second
+    block whatever the cap becomes."""
     import torch
-    log = mixed_log(600)
-    assert len(log) >= 600 * B
+    import loop_trips as LT
+    cus = LT.device_cus(gpu)
+    nb = max(LT.size_for("wal_unframe_kernel", 2, cus, 5), 600)
+    log = mixed_log(nb)
+    assert len(log) >= nb * B
+    assert LT.trips("wal_unframe_kernel", -(-len(log) // B), cus) >= 2
     check(torch, gpu, log, pay_shift=9)
 
 

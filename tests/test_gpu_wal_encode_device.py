@@ -105,12 +105,16 @@ def test_capacity(gpu):
 
 
 def test_more_blocks_than_compute_units(gpu):
-    """16 MiB of skewed records: 512 log blocks against 256 CUs, and more
-    blocks than the kernel has workgroups in flight per CU."""
+    """Skewed records over more log blocks than wal_frame_kernel has
+    workgroups: sized from the launcher's cap (tests/loop_trips.py), so every
+    workgroup takes a second block whatever the cap becomes."""
     import torch
+    import loop_trips as LT
+    cus = LT.device_cus(gpu)
+    nb = max(LT.size_for("wal_frame_kernel", 2, cus, 3), 512)
     r = W.Random(301)
     sizes, tot = [], 0
-    while tot < (16 << 20):
+    while tot < nb * B:
         sizes.append(r.skewed(17))
         tot += sizes[-1]
     payload = np.random.default_rng(14).integers(0, 256, size=tot, dtype=np.uint8).tobytes()
@@ -120,7 +124,7 @@ def test_more_blocks_than_compute_units(gpu):
     recs = [payload[int(o):int(o + n)] for o, n in zip(off, ln)]
     got, guards_ok = encode_checked(torch, gpu, payload, off, ln, 0, out_shift=9, pay_shift=4)
     want = oracle_encode(recs)
-    assert len(want) >= 512 * B
+    assert len(want) >= nb * B and LT.trips("wal_frame_kernel", -(-len(want) // B), cus) >= 2
     assert first_diff(got, want) is None, first_diff(got, want)
     assert guards_ok
 
