@@ -1,0 +1,342 @@
+// Stand-alone check of the version lookup's host twins (csrc/version.cc, whose
+// core csrc/lvk/version_read.h is the text the kernels compile too) for
+// sanitizer builds on the CPU:
+//
+//   python tests/version_cases.py dump cases.bin
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude
+//       tools/version_host_check.cc leveldb-rs_amd/csrc/version.cc -o version_host_check
+//   ./version_host_check cases.bin
+//
+// Every arena, boundary-key buffer, descriptor array and query key is a heap
+// block of exactly its size, so a read one byte outside is a
+// heap-buffer-overflow.  Four parts over the dumped cases (the shapes, the
+// damaged descriptors, the corrupted example and random consistent versions,
+// with the Python model's expected outputs: the inputs the GPU tests use, run
+// here first):
+//   1. replay: lv_version_open_host and lv_version_get_host (with and without
+//      the filters) must give the model's answers, and lv_version_file_host
+//      over every file must give back the dumped descriptor and boundary keys;
+//   2. random flips in the images, the descriptors, the lv_version_state, the
+//      tables and the filters, through the open and through the get with the
+//      damaged open's state and with the sound one;
+//   3. descriptors that belong to another version: each array of a case in
+//      turn replaced by another case's, cut to a common file count;
+//   4. lv_version_file_host over flipped images, at every capacity around the
+//      bytes it needs.
+// Whatever the bytes say, the answers stay inside the buffers.  Exits 0 when
+// everything agrees.
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "lvgpu/crc32c.h"
+#include "lvgpu/version.h"
+
+namespace {
+
+int g_fail = 0;
+#define CHECK(cond)                                                          \
+    do {                                                                     \
+        if (!(cond)) {                                                       \
+            if (g_fail < 50) std::fprintf(stderr, "%s:%d: %s failed\n", __FILE__, __LINE__, #cond); \
+            ++g_fail;                                                        \
+        }                                                                    \
+    } while (0)
+
+// a heap copy of exactly n bytes (NULL for none)
+template <class T>
+T *exact(const T *p, size_t count) {
+    if (!count) return nullptr;
+    T *q = static_cast<T *>(std::malloc(count * sizeof(T)));
+    std::memcpy(q, p, count * sizeof(T));
+    return q;
+}
+
+uint64_t g_rng = 0x9e3779b97f4a7c15ull;
+uint64_t rnd() {
+    g_rng ^= g_rng << 13;
+    g_rng ^= g_rng >> 7;
+    g_rng ^= g_rng << 17;
+    return g_rng;
+}
+
+struct Query {
+    std::string key;
+    uint64_t seq;
+    lv_version_get_result want, want_plain;
+};
+
+struct Case {
+    std::vector<uint8_t> images, bounds;
+    std::vector<lv_version_file> files;
+    std::vector<lv_sst_table> tables;
+    std::vector<lv_sst_bloom> blooms;
+    lv_version_state version;
+    std::vector<Query> queries;
+    bool regen;  // lv_version_file over the images gives the descriptors back
+};
+
+// the arrays of one lookup, each an exact-size heap block
+struct Arrays {
+    uint8_t *images, *bounds;
+    uint64_t images_bytes, bounds_bytes;
+    lv_version_file *files;
+    lv_sst_table *tables;
+    lv_sst_bloom *blooms;
+    size_t n;
+    Arrays(const Case &c, size_t n_)
+        : images(exact(c.images.data(), c.images.size())), bounds(exact(c.bounds.data(), c.bounds.size())),
+          images_bytes(c.images.size()), bounds_bytes(c.bounds.size()), files(exact(c.files.data(), n_)),
+          tables(exact(c.tables.data(), n_)), blooms(exact(c.blooms.data(), n_)), n(n_) {}
+    ~Arrays() {
+        std::free(images);
+        std::free(bounds);
+        std::free(files);
+        std::free(tables);
+        std::free(blooms);
+    }
+    Arrays(const Arrays &) = delete;
+    Arrays &operator=(const Arrays &) = delete;
+};
+
+bool read_cases(const char *path, std::vector<Case> *out) {
+    std::FILE *f = std::fopen(path, "rb");
+    if (!f) return false;
+    std::vector<uint8_t> b;
+    uint8_t buf[65536];
+    for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) b.insert(b.end(), buf, buf + n);
+    std::fclose(f);
+    size_t at = 0;
+    auto u64 = [&]() {
+        uint64_t v;
+        std::memcpy(&v, b.data() + at, 8);
+        at += 8;
+        return v;
+    };
+    auto take = [&](void *dst, size_t n) {
+        if (n) std::memcpy(dst, b.data() + at, n);
+        at += n;
+    };
+    const uint64_t cases = u64();
+    for (uint64_t i = 0; i < cases; ++i) {
+        Case c;
+        c.regen = u64() != 0;
+        c.images.resize(u64());
+        take(c.images.data(), c.images.size());
+        c.bounds.resize(u64());
+        take(c.bounds.data(), c.bounds.size());
+        const uint64_t n = u64();
+        c.files.resize(n);
+        c.tables.resize(n);
+        c.blooms.resize(n);
+        take(c.files.data(), n * sizeof(lv_version_file));
+        take(c.tables.data(), n * sizeof(lv_sst_table));
+        take(c.blooms.data(), n * sizeof(lv_sst_bloom));
+        take(&c.version, sizeof c.version);
+        c.queries.resize(u64());
+        for (Query &q : c.queries) {
+            q.key.resize(u64());
+            take(&q.key[0], q.key.size());
+            q.seq = u64();
+            take(&q.want, sizeof q.want);
+            take(&q.want_plain, sizeof q.want_plain);
+        }
+        out->push_back(std::move(c));
+    }
+    return at == b.size();
+}
+
+bool same(const lv_version_get_result &a, const lv_version_get_result &b) { return !std::memcmp(&a, &b, sizeof a); }
+
+int get(const Arrays &a, bool bloom, const lv_version_state &v, const std::string &key, uint64_t seq,
+        lv_version_get_result *r) {
+    uint8_t *k = exact(reinterpret_cast<const uint8_t *>(key.data()), key.size());
+    lv_version_state *vv = exact(&v, 1);
+    std::memset(r, 0xEE, sizeof *r);
+    const int rc = lv_version_get_host(a.images, a.images_bytes, a.files, a.tables, bloom ? a.blooms : nullptr, a.n,
+                                       a.bounds, a.bounds_bytes, vv, k, key.size(), seq, r);
+    std::free(k);
+    std::free(vv);
+    return rc;
+}
+
+// whatever the arrays say, an answer lies inside them
+void check_sane(const lv_version_get_result &r, const Arrays &a) {
+    CHECK(r.status <= LV_SST_GET_CORRUPT);
+    if (r.status == LV_SST_GET_FOUND) CHECK(r.val_off <= a.images_bytes && r.val_len <= a.images_bytes - r.val_off);
+    if (r.status != LV_SST_GET_FOUND) CHECK(r.val_off == 0 && r.val_len == 0);
+    if (r.status == LV_SST_GET_FOUND || r.status == LV_SST_GET_DELETED || r.status == LV_SST_GET_CORRUPT)
+        CHECK(r.file < a.n && r.files_read >= 1);  // (level is the descriptor's word, whatever it says)
+    else
+        CHECK(r.file == 0 && r.level == 0 && r.tag == 0 && r.block == 0);
+    if (r.status >= LV_SST_GET_BAD_SEQ && r.status <= LV_SST_GET_BAD_QUERY)
+        CHECK(r.files_read == 0 && r.seek_file == 0 && r.filtered == 0);
+    CHECK(r.files_read <= a.n && r.filtered <= r.files_read && r.seek_file <= a.n);
+}
+
+void open(const Arrays &a, lv_version_state *v) {
+    std::memset(v, 0xEE, sizeof *v);
+    CHECK(lv_version_open_host(a.images_bytes, a.files, a.tables, a.n, a.bounds, a.bounds_bytes, v) == 0);
+    CHECK(v->files == a.n && (v->status & ~31ull) == 0 && v->first_bad <= a.n && (v->first_bad == a.n) == !v->status);
+    for (uint32_t l = 0; l <= LV_NUM_LEVELS; ++l) CHECK(v->level_start[l] <= a.n && (!v->status || !v->level_start[l]));
+}
+
+void replay(const Case &c) {
+    Arrays a(c, c.files.size());
+    lv_version_state v;
+    open(a, &v);
+    CHECK(!std::memcmp(&v, &c.version, sizeof v));
+    for (const Query &q : c.queries) {
+        lv_version_get_result r;
+        CHECK(get(a, true, v, q.key, q.seq, &r) == 0 && same(r, q.want));
+        check_sane(r, a);
+        CHECK(get(a, false, v, q.key, q.seq, &r) == 0 && same(r, q.want_plain));
+    }
+    // the descriptors again, from the images: the model's files and keys
+    if (!c.regen) return;  // (a damaged descriptor is not what the images say)
+    uint8_t *keys = static_cast<uint8_t *>(std::malloc(std::max<size_t>(c.bounds.size(), 1)));
+    uint64_t used = 0;
+    for (size_t f = 0; f < a.n; ++f) {
+        lv_version_file out;
+        CHECK(lv_version_file_host(a.images, a.images_bytes, c.files[f].file_off, c.files[f].file_cap, &a.tables[f],
+                                   c.files[f].number, c.files[f].level, keys, c.bounds.size(), &used, &out) == 0);
+        CHECK(!std::memcmp(&out, &c.files[f], sizeof out));
+    }
+    CHECK(used == c.bounds.size() && (c.bounds.empty() || !std::memcmp(keys, c.bounds.data(), c.bounds.size())));
+    std::free(keys);
+}
+
+void flip(void *p, size_t bytes) {
+    if (!bytes) return;
+    uint8_t *b = static_cast<uint8_t *>(p);
+    const int flips = 1 + static_cast<int>(rnd() % 3);
+    for (int i = 0; i < flips; ++i) {
+        const size_t at = rnd() % bytes;
+        // now and then a large value, not only a neighbouring one
+        b[at] = rnd() % 4 ? static_cast<uint8_t>(rnd()) : static_cast<uint8_t>(b[at] ^ (1u << (rnd() % 8)));
+    }
+}
+
+void ask(const Case &c, const Arrays &a, const lv_version_state &damaged, int count) {
+    if (c.queries.empty()) return;
+    for (int i = 0; i < count; ++i) {
+        const Query &q = c.queries[rnd() % c.queries.size()];
+        lv_version_get_result r;
+        for (int pass = 0; pass < 4; ++pass) {
+            CHECK(get(a, pass & 1, pass & 2 ? damaged : c.version, q.key, q.seq, &r) == 0);
+            check_sane(r, a);
+        }
+    }
+}
+
+void fuzz(const Case &c, int rounds) {
+    const size_t n = c.files.size();
+    for (int round = 0; round < rounds; ++round) {
+        Arrays a(c, n);
+        lv_version_state v = c.version;
+        switch (round % 6) {
+            case 0: flip(a.images, a.images_bytes); break;
+            case 1: flip(a.files, n * sizeof(lv_version_file)); break;
+            case 2: flip(a.tables, n * sizeof(lv_sst_table)); break;
+            case 3: flip(a.blooms, n * sizeof(lv_sst_bloom)); break;
+            case 4: flip(a.bounds, a.bounds_bytes); break;
+            default: break;
+        }
+        if (round % 6 == 5) {
+            flip(&v, sizeof v);  // a state nobody validated
+        } else {
+            open(a, &v);
+        }
+        ask(c, a, v, 6);
+    }
+}
+
+// arrays of `c` with one of them taken from `o`, both cut to n files
+void foreign(const Case &c, const Case &o) {
+    const size_t n = std::min(c.files.size(), o.files.size());
+    if (!n) return;
+    for (int which = 0; which < 6; ++which) {
+        Case m = c;
+        m.files.resize(n);
+        m.tables.resize(n);
+        m.blooms.resize(n);
+        if (which == 0) m.files.assign(o.files.begin(), o.files.begin() + n);
+        if (which == 1) m.tables.assign(o.tables.begin(), o.tables.begin() + n);
+        if (which == 2) m.blooms.assign(o.blooms.begin(), o.blooms.begin() + n);
+        if (which == 3) m.images = o.images;
+        if (which == 4) m.bounds = o.bounds;
+        if (which == 5) m.version = o.version;  // and a state for other arrays
+        Arrays a(m, n);
+        lv_version_state v;
+        open(a, &v);
+        // the open's verdict, the other case's state, and c's own (all is well, for other arrays)
+        ask(m, a, v, 8);
+        lv_version_state forged = c.version;
+        forged.files = n;
+        for (uint32_t l = 0; l <= LV_NUM_LEVELS; ++l) forged.level_start[l] = std::min<uint64_t>(forged.level_start[l], n);
+        forged.level_start[LV_NUM_LEVELS] = n;
+        ask(m, a, forged, 8);
+        ask(m, a, o.version, 4);
+    }
+}
+
+void file_fuzz(const Case &c, int rounds) {
+    if (c.files.empty() || c.version.status) return;
+    for (int round = 0; round < rounds; ++round) {
+        const size_t f = rnd() % c.files.size();
+        const lv_version_file &F = c.files[f];
+        uint8_t *images = exact(c.images.data(), c.images.size());
+        lv_sst_table *t = exact(&c.tables[f], 1);
+        if (round % 3 == 0) flip(t, sizeof *t);
+        if (round % 3 != 0) flip(images + F.file_off, static_cast<size_t>(c.tables[f].file_bytes));
+        const uint64_t need = static_cast<uint64_t>(F.smallest_len) + F.largest_len;
+        const uint64_t cap = rnd() % (need + 4), start = rnd() % 3;
+        uint8_t *keys = static_cast<uint8_t *>(std::malloc(std::max<uint64_t>(cap, 1)));
+        uint64_t used = start;
+        lv_version_file out;
+        std::memset(&out, 0xEE, sizeof out);
+        const uint64_t off = round % 7 == 6 ? F.file_off + rnd() % 64 : F.file_off;  // now and then another extent
+        CHECK(lv_version_file_host(images, c.images.size(), off, F.file_cap, t, F.number, F.level, cap ? keys : nullptr,
+                                   cap, &used, &out) == 0);
+        CHECK(out.status <= LV_VERSION_FILE_BOUND_OVER && out.number == F.number && out.level == F.level);
+        if (out.status) {
+            CHECK(used == start && !out.smallest_off && !out.largest_off && !out.smallest_len && !out.largest_len);
+        } else {
+            CHECK(out.smallest_off == start && out.largest_off == start + out.smallest_len &&
+                  used == start + out.smallest_len + out.largest_len && used <= cap && out.smallest_len >= 8 &&
+                  out.largest_len >= 8);
+        }
+        std::free(keys);
+        std::free(t);
+        std::free(images);
+    }
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    if (argc != 2) {
+        std::fprintf(stderr, "usage: %s cases.bin (python tests/version_cases.py dump cases.bin)\n", argv[0]);
+        return 2;
+    }
+    std::vector<Case> cases;
+    if (!read_cases(argv[1], &cases) || cases.empty()) {
+        std::fprintf(stderr, "cannot read %s\n", argv[1]);
+        return 2;
+    }
+    size_t queries = 0;
+    for (const Case &c : cases) {
+        replay(c);
+        queries += c.queries.size();
+    }
+    for (const Case &c : cases) fuzz(c, 120);
+    for (size_t i = 0; i < cases.size(); ++i)
+        for (size_t j : {(i + 1) % cases.size(), (i + 7) % cases.size(), rnd() % cases.size()}) foreign(cases[i], cases[j]);
+    for (const Case &c : cases) file_fuzz(c, 60);
+    std::printf("version_host_check: %zu cases, %zu queries replayed, %d failures\n", cases.size(), queries, g_fail);
+    return g_fail ? 1 : 0;
+}
