@@ -206,7 +206,9 @@ int lv_device_counters(int device, uint64_t *out, size_t n);
  * scan entries (scan_cap); sb_bloom_emit, sb_bloom_big data blocks (op_cap);
  * sb_bloom_offsets filter windows (file_cap >> 11); so_validate data blocks
  * (block_cap); so_emit handles (block_cap + 2); ss_count restart runs
- * (op_cap + block_cap); sst_blocks_kernel and combine_pieces_kernel blocks.
+ * (op_cap + block_cap); sst_blocks_kernel and combine_pieces_kernel blocks;
+ * hint_len_kernel lengths (a trip is a pass of its four-way unrolled loop:
+ * 1,024 lengths a workgroup; the tail loop takes the last, partial one).
  * The one-workgroup round
  * loops (wb_tiles, wal_dec_tiles; sb_carry, ss_carry and cf_carry, in entries
  * or data blocks) report grid 1 and the units of a round.

@@ -711,6 +711,14 @@ int launch_binned(DevCtx &c, uint8_t *ws_bytes, const uint8_t *arena, const uint
 
 }  // namespace lvh
 
+// hint_len_kernel: 256 threads of four loads in flight, so a workgroup takes
+// 1,024 lengths in a trip of its unrolled loop (the tail loop takes the last,
+// partial trip a length per thread at a time).
+uint64_t lvgpu_internal::hint_len_grid(uint64_t n, uint64_t cus, uint64_t *per_trip) {
+    if (per_trip) *per_trip = 1024;
+    return std::min<uint64_t>(4 * cus, (n + 1023) / 1024);
+}
+
 using namespace lvh;
 
 extern "C" {
@@ -789,7 +797,7 @@ static int batch_device_impl(const uint8_t *d_arena, const uint64_t *d_off, cons
             const uint32_t L = hint->max_len;
             P.hident = 1u + (L <= 256u ? 0u : L <= 2048u ? 1u : L <= 32768u ? 2u : 3u);  // 1 + lvk::len_class(L)
             g_kernel = "hint_len_kernel+crc32c_classes_kernel";
-            const uint64_t lg = std::min<uint64_t>(4ull * static_cast<uint64_t>(c->cus), (n + 1023) / 1024);
+            const uint64_t lg = lvgpu_internal::hint_len_grid(n, static_cast<uint64_t>(c->cus));
             hipLaunchKernelGGL(lvk::hint_len_kernel, dim3(static_cast<uint32_t>(lg)), dim3(256), 0, s, d_len,
                                static_cast<uint64_t>(n), L, hcv.err);
             launch_classes(*c, d_seed != nullptr, P, reinterpret_cast<const uint32_t *>(d_ws), s);

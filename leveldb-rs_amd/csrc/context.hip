@@ -431,6 +431,8 @@ uint64_t lv_debug_launch_grid(const char *kernel, uint64_t units, int cus, uint6
         grid = li::sst_blocks_grid(units, c, &per);
     else if (k == "combine_pieces_kernel")
         grid = li::combine_pieces_grid(units, &per);
+    else if (k == "hint_len_kernel")
+        grid = li::hint_len_grid(units, c, &per);
     else
         return 0;
     if (units_per_workgroup_trip) *units_per_workgroup_trip = per;
@@ -440,7 +442,7 @@ uint64_t lv_debug_launch_grid(const char *kernel, uint64_t units, int cus, uint6
 const char *lv_debug_launch_grid_names(void) {
     return "hash_kernel wb_count wb_emit wb_tiles wal_frame_kernel wal_unframe_kernel wal_dec_classify wal_dec_reduce "
            "wal_dec_apply wal_dec_tiles wal_unsort sb_bloom_emit sb_bloom_big sb_bloom_offsets so_validate so_emit "
-           "ss_count sst_blocks_kernel sb_carry ss_carry cf_carry combine_pieces_kernel";
+           "ss_count sst_blocks_kernel sb_carry ss_carry cf_carry combine_pieces_kernel hint_len_kernel";
 }
 
 void *lv_host_alloc(size_t bytes) {

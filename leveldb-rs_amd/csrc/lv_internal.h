@@ -145,6 +145,7 @@ uint64_t so_grid(uint64_t lanes, uint64_t *per_trip = nullptr);                 
 uint64_t ss_count_grid(uint64_t runs, uint64_t *per_trip = nullptr);            // ss_count (restart runs, <= run_cap)
 uint64_t sst_blocks_grid(uint64_t blocks, uint64_t cus, uint64_t *per_trip = nullptr);      // sst_blocks_kernel (wave claims)
 uint64_t combine_pieces_grid(uint64_t blocks, uint64_t *per_trip = nullptr);                // combine_pieces_kernel
+uint64_t hint_len_grid(uint64_t n, uint64_t cus, uint64_t *per_trip = nullptr);             // hint_len_kernel (a trip: its four loads)
 // The one-workgroup round loops: entries a round takes (the grid is 1).
 uint64_t wb_tiles_round();       // wb_tiles: records per round
 uint64_t wal_dec_tiles_round();  // wal_dec_tiles: scan entries per round

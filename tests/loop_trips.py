@@ -59,9 +59,10 @@ def device_cus(gpu):
 # sized for, the trips asked of that one, the ragged extra, the trips this
 # kernel must make at that size).  tests/test_loop_trips.py holds every row to
 # its trips at 256 compute units; the GPU tests assert them for their device.
-# A kernel the suite cannot drive round in a few seconds sizes itself for two
-# trips, so that its row still says what that would take (the
-# loop-trip audit).
+# A kernel whose test adds to its size in its own way (ss_count: a full tile
+# and a ragged one; hint_len_kernel: three strides) or rides on another
+# module's input (sb_bloom_offsets: the table of test_gpu_positions64.py) has
+# the smallest size of its trips here (the loop-trip audit).
 PLAN = {
     "hash_kernel": ("hash_kernel", 3, 64 * 5 + 17, 3),
     "wb_emit": ("wb_emit", 3, 300, 3),
@@ -85,9 +86,36 @@ PLAN = {
     "ss_carry": ("sb_carry", 2, 2517, 2),
     "cf_carry": ("sb_carry", 2, 2517, 2),
     "combine_pieces_kernel": ("combine_pieces_kernel", 2, 903, 2),
+    "hint_len_kernel": ("hint_len_kernel", 3, 300, 3),  # (the GPU test adds three strides: hint_len_shape)
 }
 
 
 def planned_size(kernel, cus):
     by, want, extra, _ = PLAN[kernel]
     return size_for(by, want, cus, extra)
+
+
+# hint_len_kernel's loop has two levels: thread t of the grid's `stride`
+# threads reads len[t + q * stride], four values of q in flight in a pass of
+# the unrolled loop for as long as all four lie below n, the rest one at a time
+# in the tail loop.
+def hint_len_shape(cus, ragged=300):
+    """(n, stride): two full trips of the unrolled loop, then three strides and
+    `ragged` lengths more, so thread t makes two unrolled passes and three
+    tail iterations, and the threads t < ragged a third unrolled pass and no
+    tail."""
+    n = size_for("hint_len_kernel", 3, cus) - 1  # two full trips of every workgroup
+    grid, per = grid_of("hint_len_kernel", n, cus)
+    stride = grid * per // 4
+    assert n == 8 * stride and 0 < ragged < stride
+    n += 3 * stride + ragged
+    assert grid_of("hint_len_kernel", n, cus) == (grid, per)
+    return n, stride
+
+
+def hint_len_place(i, n, stride):
+    """Where the loop reads len[i]: ("unrolled", pass, slot) or ("tail",
+    iteration, 0), with the passes the reading thread makes."""
+    t, q = i % stride, i // stride
+    passes = max(0, -(-(n - t - 3 * stride) // (4 * stride)))
+    return ("unrolled", q // 4, q % 4) if q // 4 < passes else ("tail", q - 4 * passes, 0)

@@ -187,3 +187,79 @@ def bloom_items(n):
             items.append((b"key%07d" % i, tag(10 + i % 7), bytes([65 + i % 26]) * (vlen + i % 3)))
             i += 3  # (keys 3 i + 1 are absent)
     return items[:n]
+
+
+# ---- Table scan: a restart run per entry, known by construction ----
+SCAN_BLOCK = 4096  # block_size; restart_interval is 1
+
+
+def scan_ops(n):
+    """(payload, ops) of n entries already in memtable order: entry i has the
+    user key i as 8 big-endian bytes, sequence i + 1, every 7th a deletion, and
+    otherwise a value of (i // 500) % 3 bytes, the key's last ones (the low
+    bytes of i): stretches of entries of one size, so the blocks hold from 166
+    to 178 entries and their edges move through the scan tiles."""
+    from lvgpu.write_batch import OP_DTYPE
+    i = np.arange(n, dtype=np.uint64)
+    payload = i.astype(">u8").tobytes()
+    dele = i % np.uint64(7) == 6
+    ops = np.zeros(n, dtype=OP_DTYPE)
+    ops["tag"] = ((i + np.uint64(1)) << np.uint64(8)) | (~dele).astype(np.uint64)
+    ops["key_off"], ops["key_len"] = np.uint64(8) * i, 8
+    ops["val_len"] = np.where(dele, 0, i // np.uint64(500) % np.uint64(3)).astype(np.uint32)
+    ops["val_off"] = ops["key_off"] + np.uint64(8) - ops["val_len"].astype(np.uint64)
+    return payload, ops
+
+
+def scan_layout(val_len):
+    """The data blocks of scan_ops' table under block_size SCAN_BLOCK and
+    restart_interval 1, by the builder's rule in numpy: an entry is 3 length
+    bytes, the 16-byte internal key and the value, with a 4-byte restart of its
+    own; a block ends with the first entry that brings buffer + restarts + 4
+    to the block size.  (first entry of each block and n behind them, block
+    offsets, block sizes, the offset of every entry in its block)."""
+    size = 19 + np.asarray(val_len, dtype=np.int64)
+    n = size.size
+    c = np.cumsum(size + 4)
+    first, a = [], 0
+    while a < n:
+        first.append(a)
+        a = int(np.searchsorted(c, (c[a - 1] if a else 0) + SCAN_BLOCK - 4)) + 1
+    first = np.array(first + [n], dtype=np.int64)
+    b = np.concatenate([[0], np.cumsum(size)])
+    counts = np.diff(first)
+    bsize = b[first[1:]] - b[first[:-1]] + 4 * counts + 4
+    boff = np.concatenate([[0], np.cumsum(bsize + 5)[:-1]])
+    at = b[:-1] - np.repeat(b[first[:-1]], counts)
+    return first, boff, bsize, at
+
+
+# ---- Bloom build: one-entry 4 KiB blocks and a few crowded ones ----
+BLOOM_BIG_BLOCK = 4096  # block_size
+BLOOM_BIG_CROWD = 280   # entries without a value in front of a crowded block's big entry
+
+
+def bloom_big_items(nblocks, crowded):
+    """(items in key order, {crowded block: (index of its first item, items)})
+    for block_size 4096: every block ends with an entry whose value fills a
+    block by itself, so a block is one entry of about 4,125 bytes and every
+    second or third 2 KiB window holds one block start; the blocks named in
+    `crowded` begin with BLOOM_BIG_CROWD more entries of about 12 bytes
+    (prefix-compressed 10-byte keys, no value), so at 64 bits per key the
+    filter of such a block's window is beyond the 2,048 bytes a wave of
+    sb_bloom_emit builds in LDS, between the 9-byte filters of its neighbours.
+    Keys are key%07d of multiples of 3."""
+    from memtable_cases import tag
+    items, where, i = [], {}, 0
+
+    def put(vlen):
+        nonlocal i
+        items.append((b"key%07d" % i, tag(10 + i % 7), bytes([65 + i % 26]) * vlen))
+        i += 3  # (keys 3 i + 1 are absent)
+    for b in range(nblocks):
+        if b in crowded:
+            where[b] = (len(items), BLOOM_BIG_CROWD + 1)
+            for _ in range(BLOOM_BIG_CROWD):
+                put(0)
+        put(BLOOM_BIG_BLOCK - 6 + i % 3)
+    return items, where

@@ -335,6 +335,69 @@ def test_bloom_build_three_trips(gpu, cus):
         assert bad.size == 0, (name, int(bad[0]), int(got[name][bad[0]]), int(w[bad[0]]))
 
 
+def test_bloom_big_three_trips(gpu, cus):
+    """lv_sst_build_bloom_device at 64 bits per key over one-entry 4 KiB blocks,
+    enough for a third trip of sb_bloom_big's waves, with one crowded block
+    (281 keys: a filter of 2,249 bytes, beyond the wave's LDS) on each of the
+    three trips, so the kernel sets bits on every trip and not only skips.  The
+    crowded filters lie between 9-byte filters of their neighbours and start
+    and end off the dword grid: the atomic ORs on shared dwords must keep the
+    neighbours' bytes.  Every byte of the image and both totals against the
+    serial Python model; then lv_sst_get_bloom_device over the crowded windows:
+    every key they hold is found, and every absent key is filtered or not as
+    the Python model's reader decides for that key."""
+    import torch
+    import lvgpu.table as T
+    import sst_bloom_cases as SB
+    import sst_get_cases as G
+    nb = LT.size_for("sb_bloom_big", 3, 1, 7)  # (the cap is a constant: any cus)
+    grid, per = LT.grid_of("sb_bloom_big", nb, 1)
+    crowded = [per * 100 + 1, grid * per + per * 511 + 2, 2 * grid * per + 3]  # a wave 1, a wave 2 and a wave 3
+    assert [b // (grid * per) for b in crowded] == [0, 1, 2] and crowded[-1] + 1 < nb
+    items, where = LC.bloom_big_items(nb, set(crowded))
+    # the launch sizes its grid by op_cap, the entries; the loop runs over the data blocks
+    assert LT.grid_of("sb_bloom_big", len(items), 1) == (grid, per) and -(-nb // per) > 2 * grid
+    _need("sb_bloom_big", nb, 1, 3)
+    _need("sb_bloom_emit", nb, 1, 3)
+    built, payload, ops, want = SB.check_device(torch, gpu, items, LC.BLOOM_BIG_BLOCK, 16, 64, tag_="big filters, three trips")
+    image, handles, tot, btot = want
+    assert tot["data_blocks"] == nb and btot["filter_keys"] == len(items)
+    fo, fs = handles[-3]
+    arr = fo + fs - 5 - 4 * btot["filters"]
+    start = lambda w: G.le32(image, arr + 4 * w)
+    sizes = np.diff([start(w) for w in range(btot["filters"] + 1)])  # (the word behind the array is the array's offset)
+    big = np.nonzero(sizes > T.SB_BLOOM_LDS + 1)[0].tolist()
+    assert big == [handles[b][0] >> SB.BASE_LG for b in crowded], (big, crowded)  # the model: exactly these windows
+    ragged = 0
+    for b, w in zip(crowded, big):
+        assert sizes[w] == (where[b][1] * 64 + 7) // 8 + 1
+        small = [int(s) for s in sizes[w - 4:w + 5] if 0 < s <= T.SB_BLOOM_LDS + 1]
+        assert len(small) >= 2 and set(small) == {9}, small  # one key, 64 bits and the k byte, on either side
+        ragged += (start(w) % 4 != 0) + (start(w + 1) % 4 != 0)
+    assert ragged >= 4
+    # the filtered get over the crowded windows
+    held, absent = [], []
+    for b in crowded:
+        at, k = where[b]
+        held += [(items[j][0], items[j][1] >> 8) for j in range(at, at + k)]
+        absent += [(b"key%07d" % (int(items[j][0][3:]) + 1), 1 << 40) for j in range(at, at + k, 2)]
+    queries = held + absent
+    table, bloom, wants = SB.host_answers(image, queries)
+    assert (table, bloom, wants[len(held):]) == SB.model_answers(image, absent)  # the Python reader, key by key
+    assert bloom["present"] == 1 and all(w["status"] == G.FOUND for w in wants[: len(held)])
+    assert all(w["status"] == G.ABSENT for w in wants[len(held):])
+    assert sum(w["reserved"] == SB.FILTERED for w in wants[len(held):]) >= len(absent) - 3  # (64 bits a key)
+    op, bloom_t, owner = SB.open_both(torch, gpu, image, shift=3)
+    qk, off, ln, sq, _ = G.pack_queries(queries, bad_query=False)
+    got = SB.run_get(torch, gpu, op, bloom_t, qk, off, ln, sq)
+    assert op.sync() == table and T.bloom_dict(bloom_t) == bloom
+    for name in G.RESULT_FIELDS:
+        w = np.array([x[name] for x in wants], dtype=np.uint64)
+        bad = np.nonzero(got[name].astype(np.uint64) != w)[0]
+        assert bad.size == 0, (name, int(bad[0]), int(got[name][bad[0]]), int(w[bad[0]]))
+    del built, op, bloom_t, owner
+
+
 # ---- so_validate / so_emit --------------------------------------------------------
 def test_table_open_two_trips(gpu, cus):
     """lv_sst_open_device over a table of one-entry blocks, enough for a second
@@ -459,6 +522,109 @@ def test_carry_scans_second_round(gpu):
     assert np.array_equal(sc.ops(), want_ops[:kept]) and sc.arena() == want_arena[: want_s["arena_bytes"]].tobytes()
 
 
+# ---- ss_count: the second trip over the tiles of restart runs ---------------------
+def test_table_scan_second_trip(gpu):
+    """lv_sst_scan_device over a table of more restart runs than ss_count has
+    workgroups times a tile: restart_interval 1 makes every entry a run, and
+    behind the 4,096 tiles of the first trip come a full tile and a ragged one,
+    so two workgroups fill s_e / s_b a second time.  Memtable build -> table
+    build -> verify -> open -> scan on the device.  The scan of a build is the
+    sorted op table, here the input itself: every op's tag and lengths, its
+    offsets (the arena is packed) and its key and value bytes gathered from
+    the arena are compared on the device, for every entry.  The built image is
+    tied to the Python model on the blocks that a prefix of the entries fully
+    determines, and every data block's handle to the builder's rule.  Then one
+    byte: an entry's non_shared length, in a run that only a second-trip lane
+    walks, made to overrun its run and the entries behind it: CORRUPT, nothing
+    written, as lv_sst_scan_host says of the same flip in the small image."""
+    import torch
+    import lvgpu.table as T
+    import memtable_cases as M
+    import sst_build_cases as S
+    first_two = LT.size_for("ss_count", 2, 1)
+    _, per = LT.grid_of("ss_count", first_two, 1)
+    n = LT.size_for("ss_count", 2, 1, per + 299)  # the first trip's tiles, a full tile, 300 runs
+    payload, ops = LC.scan_ops(n)
+    first, boff, bsize, at = LC.scan_layout(ops["val_len"])
+    nb = len(first) - 1
+    grid, per = LT.grid_of("ss_count", n + nb, 1)  # the launch: run_cap = op_cap + block_cap; the loop: the runs
+    assert per == T.SS_TILE and -(-n // per) == grid + 2 and n % per == 300
+    _need("ss_count", n, 1, 2)
+    table, buf = M.run_build(torch, gpu, payload, ops, shift=3)
+    assert table.sync_totals() == dict(entries=n, user_keys=n, status=0)
+    assert bool((table.order_t[:n] == torch.arange(n, dtype=torch.int32, device=gpu)).all())
+    built = T.build_device(table, block_size=LC.SCAN_BLOCK, restart_interval=1, block_cap=nb, fill=M.CANARY, guard=M.GUARD)
+    tot = built.sync_totals()
+    assert (tot["entries"], tot["data_blocks"], tot["status"]) == (n, nb, 0)
+    fb = tot["file_bytes"]
+    hv = built.handles_view()
+    want_h = torch.from_numpy(np.stack([boff, bsize], axis=1)).to(gpu)
+    assert torch.equal(hv[:nb], want_h), "data block handles differ from the builder's rule"
+    assert tot["metaindex_offset"] == int(boff[-1] + bsize[-1]) + 5
+    # the Python model on a prefix: all of its blocks but the last are the table's first blocks
+    pp, po = LC.scan_ops(4000)
+    image_p, handles_p, _ = S.model_build(pp, po, LC.SCAN_BLOCK, 1)
+    k = len(handles_p) - 3
+    end = handles_p[k - 1][0] + handles_p[k - 1][1] + 5
+    assert k >= 20 and built.file_t[:end].cpu().numpy().tobytes() == image_p[:end]
+    st = T.verify_blocks(built.file_t[:fb], hv)
+    assert bool((st == T.BLOCK_OK).all()), torch.nonzero(st != T.BLOCK_OK)[:8].tolist()
+    op = T.open_device(built.file_t[:fb], built.totals[2:3], built.totals[7:8], block_cap=nb, fill=M.CANARY, guard=M.GUARD)
+    opened = op.sync()
+    assert (opened["data_blocks"], opened["file_bytes"], opened["status"]) == (nb, fb, 0)
+    arena_bytes = int(ops["key_len"].sum(dtype=np.uint64) + ops["val_len"].sum(dtype=np.uint64))
+    sc = T.scan_device(op, arena_cap=arena_bytes, op_cap=n, block_cap=nb, fill=M.CANARY, guard=M.GUARD)
+    assert sc.sync() == dict(entries=n, arena_bytes=arena_bytes, table_entries=n, table_bytes=arena_bytes, data_blocks=nb,
+                             runs=n, reserved=0, status=0)
+    from write_batch_cases import tail_is_canary
+    assert tail_is_canary(sc.ops_t, 32 * n) and tail_is_canary(sc.arena_t, arena_bytes)
+    got = sc.ops_t[: 32 * n].view(torch.int64).view(n, 4)
+    vlen = torch.from_numpy(ops["val_len"].astype(np.int64)).to(gpu)
+
+    def same(name, g, w):
+        bad = torch.nonzero(g != w)
+        assert bad.numel() == 0, f"{name}: {bad.shape[0]} entries differ, the first is entry {int(bad[0][0])} of {n}"
+    same("tag", got[:, 0], torch.from_numpy(ops["tag"].view(np.int64)).to(gpu))
+    same("key_len and val_len", got[:, 3], 8 + (vlen << 32))
+    koff = torch.cumsum(8 + vlen, 0) - (8 + vlen)
+    same("key_off", got[:, 1], koff)
+    same("val_off", got[:, 2], koff + 8)
+    keys = torch.frombuffer(bytearray(payload), dtype=torch.uint8).to(gpu).view(n, 8)
+    arena = sc.arena_t
+    same("key bytes", arena[got[:, 1, None] + torch.arange(8, device=gpu)], keys)
+    for j in (0, 1):  # the value: the key's last val_len bytes
+        has = torch.nonzero(vlen > j)[:, 0]
+        assert has.numel() > n // 4
+        same(f"value byte {j}", arena[got[has, 2] + j], keys[has, 8 - vlen[has] + j])
+    del keys, got, koff, want_h
+    # the damage: the last entry of a block of the first tile of the second trip
+    blk = int(np.searchsorted(first, grid * per + 500, side="right"))
+    r = int(first[blk + 1]) - 1
+    assert grid * per <= r < (grid + 1) * per and r // per - grid == 0 and r < n
+    pos = int(boff[blk] + at[r]) + 1
+    assert int(built.file_t[pos]) == 16 and int(built.file_t[pos - 1]) == 0
+    hurt = built.file_t[:fb].clone()
+    hurt[pos] = 0xFF
+    op2 = T.open_device(hurt, built.totals[2:3], built.totals[7:8], block_cap=nb, fill=M.CANARY, guard=M.GUARD)
+    assert op2.sync() == opened  # (the open reads the index, not the data blocks)
+    sc2 = T.scan_device(op2, arena_cap=arena_bytes, op_cap=n, block_cap=nb, fill=M.CANARY, guard=M.GUARD)
+    corrupt = dict(entries=0, arena_bytes=0, table_entries=0, table_bytes=0, data_blocks=nb, runs=0, reserved=0,
+                   status=T.SCAN_CORRUPT)
+    assert sc2.sync(check=False) == corrupt
+    assert tail_is_canary(sc2.ops_t, 0) and tail_is_canary(sc2.arena_t, 0), "written to under a status"
+    # the same flip in the prefix's image, by the host twin
+    f4, o4, _, a4 = LC.scan_layout(po["val_len"])
+    small = bytearray(image_p)
+    at4 = int(o4[3] + a4[f4[4] - 1]) + 1
+    assert small[at4] == 16
+    small[at4] = 0xFF
+    table_p, _ = T.open_host(bytes(small), handles=False)
+    assert table_p["status"] == 0
+    want_c = T.scan_host(bytes(small), table_p, arena_cap=1 << 17, op_cap=4000)[0]
+    assert want_c == dict(corrupt, data_blocks=table_p["data_blocks"]) and T.scan_host(image_p, table_p)[0]["status"] == 0
+    del table, buf, built, op, op2, sc, sc2, hurt, arena, vlen
+
+
 # ---- combine_pieces_kernel ---------------------------------------------------------
 def test_combine_pieces_second_trip(gpu, cus):
     """lv_crc32c_batch_strided over more split blocks than combine_pieces_kernel
@@ -484,6 +650,62 @@ def test_combine_pieces_second_trip(gpu, cus):
                      for i in range(n)], dtype=np.uint32)
     bad = np.nonzero(got != want)[0]
     assert bad.size == 0, f"{bad.size} CRCs differ, the first is block {int(bad[0])}"
+
+
+# ---- hint_len_kernel ---------------------------------------------------------------
+def test_hint_len_three_passes(gpu, cus):
+    """lv_crc32c_batch_device_hint with LV_HINT_UNIFORM over eleven strides and
+    300 lengths, laid end to end from arena offset 5 (not the aligned path):
+    every thread of hint_len_kernel makes two passes of its unrolled loop and
+    three tail iterations, the first 300 threads a third pass and no tail.  The
+    clean call reports nothing and every CRC is the oracle's; one length of
+    L - 1 at each kind of place in the two loops is reported as
+    LV_HINT_ERR_NOT_UNIFORM and nothing else, and the word is cleared."""
+    import torch
+    import lvgpu
+    n, stride = LT.hint_len_shape(cus, ragged=300)
+    _need("hint_len_kernel", n, cus, 3)
+    assert LT.trips("hint_len_kernel", n - 301, cus) == 3 and LT.trips("hint_len_kernel", n + 4 * stride, cus) == 4
+    L = 40
+    lens = np.full(n, L, dtype=np.uint32)
+    offs = 5 + L * np.arange(n, dtype=np.uint64)
+    a = torch.empty(5 + n * L + 16, dtype=torch.uint8, device=gpu)
+    lvgpu.fill_splitmix(a, 0, 0x41E7)
+    hint = lvgpu.hint_for(lens)
+    assert hint.uniform == lvgpu.HINT_UNIFORM and hint.max_len == L and hint.total_bytes == n * L
+    o = torch.from_numpy(offs.view(np.int64)).to(gpu)
+    ln = torch.from_numpy(lens.view(np.int32)).to(gpu)
+    lvgpu.batch_check()
+    out = lvgpu.batch_hint(a, o, ln, hint, masked=True)
+    assert lvgpu.last_kernel() == "hint_len_kernel+crc32c_classes_kernel"
+    lvgpu.batch_check()
+    got = out.cpu().numpy().view(np.uint32)
+    want = np.zeros(n, dtype=np.uint32)
+    host = a.cpu().numpy()
+    W.lib().oracle_batch(host.ctypes.data, offs.ctypes.data, lens.ctypes.data, None, want.ctypes.data, n, 1)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, f"{bad.size} CRCs differ, the first is buffer {int(bad[0])}"
+    t0 = stride // 2 + 77  # a thread with a tail, in a workgroup of the middle of the grid
+    assert 300 <= t0 < stride
+    lies = {t0 + (4 * u + s) * stride: ("unrolled", u, s) for u in (0, 1) for s in range(4)}
+    lies.update({7 + 9 * stride: ("unrolled", 2, 1), n - 1: ("unrolled", 2, 3)})
+    lies.update({t0 + (8 + k) * stride: ("tail", k, 0) for k in range(3)})
+    lies.update({stride - 1: ("unrolled", 0, 0), stride: ("unrolled", 0, 1),         # either side of a stride
+                 10 * stride - 1: ("tail", 1, 0), 10 * stride: ("unrolled", 2, 2)})  # ... and of one in the tail
+    assert len(lies) == 17
+    for i, place in sorted(lies.items()):
+        assert 0 <= i < n and LT.hint_len_place(i, n, stride) == place, (i, place)
+        ln[i] = L - 1
+        lvgpu.batch_hint(a, o, ln, hint, masked=True, out=out)
+        assert lvgpu.last_kernel() == "hint_len_kernel+crc32c_classes_kernel"
+        with pytest.raises(lvgpu.HintViolation) as ei:
+            lvgpu.batch_check()
+        assert ei.value.violations == lvgpu.HINT_ERR_NOT_UNIFORM, (i, place, hex(ei.value.violations))
+        ln[i] = L
+        lvgpu.batch_hint(a, o, ln, hint, masked=True, out=out)
+        lvgpu.batch_check()  # the word was cleared, and the lengths are the hint's again
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), want)
+    del a, o, ln, out
 
 
 def test_peak_device_memory(gpu, hash_case, wal_blocks):

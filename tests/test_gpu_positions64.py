@@ -566,9 +566,19 @@ def test_big_table_build(gpu, big_table):
     """Totals, handles and every byte of the image against the sparse model.
     The two blocks of more than 2^31 bytes end off the 16-byte grid with a
     nonzero byte in their last granule: their trailers pin the CRC walk's tail
-    for a unit that long."""
+    for a unit that long.  The filter block is one of the compared segments,
+    its offset array included: with a 2 KiB window to every filter, the lanes
+    of sb_bloom_offsets go round their capped grid several times here."""
     import torch
+    import loop_trips as LT
     model, built = big_table["model"], big_table["built"]
+    filters = model.bloom_totals["filters"]
+    grid, per = LT.grid_of("sb_bloom_offsets", built.file_cap >> 11, 1)  # the launch: sized by file_cap
+    assert filters == len(model.filter.offsets) == model.bloom()["num"] and -(-filters // per) >= 2 * grid
+    assert LT.grid_of("sb_bloom_offsets", filters, 1) == (grid, per) and LT.trips("sb_bloom_offsets", filters, 1) >= 2
+    array = model.bloom_totals["filter_offset"] + model.bloom()["array_offset"]
+    assert any(not isinstance(seg, tuple) and at <= array and array + 4 * filters <= at + len(seg)
+               for at, seg in model.placed()), "the offset array is not inside a compared segment"
     big = [(o, sz) for o, sz in model.handles if sz > (1 << 31)]
     assert len(big) == 2 and all((o + sz) % 16 >= 4 for o, sz in big)
     assert big_table["tot"] == model.totals and built.sync_bloom_totals() == model.bloom_totals

@@ -63,10 +63,54 @@ def test_the_known_caps_at_256_compute_units():
               "wal_dec_tiles": 256 * 1024, "wal_unsort": 256 * 1024, "sb_bloom_emit": 4096, "sb_bloom_big": 4096,
               "sb_bloom_offsets": 1024 * 256, "so_validate": 2048 * 256, "so_emit": 2048 * 256,  # (so_emit: 524,286 blocks + 2)
               "ss_count": 4096 * 1024, "sst_blocks_kernel": 256 * 16, "sb_carry": 65536, "ss_carry": 65536,
-              "cf_carry": 65536, "combine_pieces_kernel": 4096}
+              "cf_carry": 65536, "combine_pieces_kernel": 4096,
+              "hint_len_kernel": 4 * 256 * 1024}  # (a thread's second length: above 4 * 256 * 256)
     assert set(second) == set(lvgpu.launch_grid_names())
     for k, last_single in second.items():
         assert LT.size_for(k, 2, 256) == last_single + 1, k
+
+
+def _walk_hint_len(n, grid):
+    """hint_len_kernel's two loops as written (csrc/classes.hip), for every
+    thread of the grid: {index: place}, and the most passes (unrolled ones,
+    and one more where a tail follows) any thread makes."""
+    stride, seen, most = grid * 256, {}, 0
+    for t in range(stride):
+        i, u = t, 0
+        while i + 3 * stride < n:
+            for slot in range(4):
+                assert i + slot * stride not in seen
+                seen[i + slot * stride] = ("unrolled", u, slot)
+            i, u = i + 4 * stride, u + 1
+        k = 0
+        while i < n:
+            assert i not in seen
+            seen[i] = ("tail", k, 0)
+            i, k = i + stride, k + 1
+        most = max(most, u + (k > 0))
+    return seen, most
+
+
+@pytest.mark.parametrize("cus", [1, 2])
+def test_hint_len_grid_against_a_walk_of_its_loops(cus):
+    """The grid query, trips() and hint_len_place() against the kernel's own
+    two-level loop, at the shape the GPU test uses and around its edges."""
+    n0, stride = LT.hint_len_shape(cus, ragged=300)
+    assert stride == 4 * cus * 256 and n0 == 11 * stride + 300
+    for n in (1, 255, 1024, 1025, 3 * stride, 3 * stride + 1, 4 * stride, 4 * stride + 1, 8 * stride, n0, n0 + 4 * stride):
+        grid, per = LT.grid_of("hint_len_kernel", n, cus)
+        assert per == 1024 and grid == min(4 * cus, -(-n // 1024))
+        seen, most = _walk_hint_len(n, grid)
+        assert sorted(seen) == list(range(n))  # every length read, and once
+        assert LT.trips("hint_len_kernel", n, cus) == most, n
+        if grid * 256 == stride:
+            for i in set(range(0, n, 97)) | {n - 1}:
+                assert LT.hint_len_place(i, n, stride) == seen[i], (n, i)
+    seen, _ = _walk_hint_len(n0, 4 * cus)
+    at = lambda t: [seen[t + q * stride] for q in range(12) if t + q * stride < n0]
+    two_and_three = [("unrolled", u, s) for u in (0, 1) for s in range(4)] + [("tail", k, 0) for k in range(3)]
+    assert at(300) == at(stride - 1) == two_and_three
+    assert at(0) == at(299) == [("unrolled", u, s) for u in (0, 1, 2) for s in range(4)]
 
 
 @pytest.mark.parametrize("kernel", sorted(LT.PLAN))

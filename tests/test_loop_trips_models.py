@@ -58,6 +58,48 @@ def test_wal_tiling_is_the_model_of_three_repetitions():
         assert pay == b"".join(want[0]) and offs.tolist() == want[1] and reps == want[2] and dropped == want[3]
 
 
+def test_scan_layout_is_the_model_build_of_a_prefix():
+    """scan_ops is in memtable order and scan_layout places its blocks and
+    entries where the Python table model does."""
+    import memtable_cases as M
+    import sst_build_cases as S
+    n = 5000
+    payload, ops = LC.scan_ops(n)
+    assert M.model_order(payload, ops) == list(range(n))
+    assert sorted(set(ops["val_len"].tolist())) == [0, 1, 2] and (ops["tag"] & 0xFF == 0).sum() == n // 7
+    assert all(M.key_of(payload, o)[8 - int(o["val_len"]):] == payload[int(o["val_off"]):int(o["val_off"]) + int(o["val_len"])]
+               for o in ops[:50])
+    image, handles, tot = S.model_build(payload, ops, LC.SCAN_BLOCK, 1)
+    first, boff, bsize, at = LC.scan_layout(ops["val_len"])
+    assert tot["data_blocks"] == len(first) - 1 > 20 and len(set(np.diff(first).tolist())) > 2  # the counts drift
+    assert [(int(o), int(s)) for o, s in zip(boff, bsize)] == handles[:-2]
+    for blk in (0, 7, len(first) - 2):
+        for i in (first[blk], first[blk] + 1, first[blk + 1] - 1):
+            e = int(boff[blk] + at[i])
+            key = M.key_of(payload, ops[i]) + int(ops["tag"][i]).to_bytes(8, "little")
+            assert image[e:e + 19] == bytes([0, 16, int(ops["val_len"][i])]) + key, (blk, i)
+    # a longer table begins with the same blocks: all of the prefix's but its last
+    f2, o2, s2, _ = LC.scan_layout(LC.scan_ops(n + 999)[1]["val_len"])
+    k = len(first) - 2
+    assert np.array_equal(f2[:k + 1], first[:k + 1]) and np.array_equal(o2[:k], boff[:k]) and np.array_equal(s2[:k], bsize[:k])
+
+
+def test_bloom_big_items_crowd_their_windows():
+    import loop_trips as LT
+    import sst_bloom_cases as SB
+    from lvgpu.table import SB_BLOOM_LDS
+    from memtable_cases import make_table
+    crowded = {3, 40}
+    items, where = LC.bloom_big_items(60, crowded)
+    assert [k for k, _, _ in items] == sorted({k for k, _, _ in items}) and len(items) == 60 + 2 * LC.BLOOM_BIG_CROWD
+    payload, ops = make_table(items)
+    image, handles, tot, btot = SB.model_build(payload, ops, 64, LC.BLOOM_BIG_BLOCK, 16)
+    assert tot["data_blocks"] == 60  # a crowded block holds its big entry too
+    assert sorted(where) == sorted(crowded) and all(items[at + k - 1][2] and not items[at][2] for at, k in where.values())
+    assert len(SB.create_filter([b"k"], 64)) == 9  # a one-entry block's filter: 64 bits and the k byte
+    assert len(SB.create_filter([k for k, _, _ in items[:LC.BLOOM_BIG_CROWD + 1]], 64)) > SB_BLOOM_LDS + 1
+
+
 def test_bloom_items_spread_their_blocks_over_the_windows():
     import loop_trips as LT
     import sst_bloom_cases as SB

@@ -5,6 +5,8 @@
 //       tools/compact_host_check.cc leveldb-rs_amd/csrc/compact.cc leveldb-rs_amd/csrc/memtable.cc
 //       -o compact_host_check && ./compact_host_check
 //
+// tests/test_host_checks.py builds it this way and runs it with the CPU suite.
+//
 // Every payload, op array, order, range array and key block is a heap block of
 // exactly its size, so a read or write one byte outside is a
 // heap-buffer-overflow.  Three parts:

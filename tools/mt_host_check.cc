@@ -4,6 +4,8 @@
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude
 //       tools/mt_host_check.cc leveldb-rs_amd/csrc/memtable.cc -o mt_host_check && ./mt_host_check
 //
+// tests/test_host_checks.py builds it this way and runs it with the CPU suite.
+//
 // Every payload is copied into a heap buffer of exactly its size, so a read
 // one byte past it is a heap-buffer-overflow.  Inputs: corner keys (the empty
 // key, lengths around 8, zero padding, bytes 0x7f / 0x80 / 0xff, long common

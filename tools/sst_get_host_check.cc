@@ -7,6 +7,9 @@
 //       leveldb-rs_amd/csrc/sst_format.cc leveldb-rs_amd/csrc/memtable.cc leveldb-rs_amd/csrc/crc32c_scalar.cc
 //       -o sst_get_host_check && ./sst_get_host_check [cases.bin]
 //
+// tests/test_host_checks.py builds it this way and runs it on the dump with
+// the CPU suite.
+//
 // Every image, handle array and query key is a heap block of exactly its
 // size, so a read one byte outside is a heap-buffer-overflow.  Three parts:
 //   1. tables built by lv_sst_build_host (the corner shapes of the format and

@@ -5,6 +5,7 @@
 //       tools/sst_host_check.cc leveldb-rs_amd/csrc/sst_build.cc leveldb-rs_amd/csrc/sst_format.cc
 //       leveldb-rs_amd/csrc/memtable.cc leveldb-rs_amd/csrc/crc32c_scalar.cc -o sst_host_check && ./sst_host_check
 //
+// tests/test_host_checks.py builds it this way and runs it with the CPU suite.
 // (sst_format.cc reports its errors through lvgpu_internal::set_error, which
 // lives in a HIP unit; this file supplies a stub.)  Every payload, file and
 // handle array is a heap buffer of exactly its size, so a read or write one

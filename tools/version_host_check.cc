@@ -7,6 +7,9 @@
 //       tools/version_host_check.cc leveldb-rs_amd/csrc/version.cc -o version_host_check
 //   ./version_host_check cases.bin
 //
+// tests/test_host_checks.py builds it this way and runs it on the dump with
+// the CPU suite.
+//
 // Every arena, boundary-key buffer, descriptor array and query key is a heap
 // block of exactly its size, so a read one byte outside is a
 // heap-buffer-overflow.  Four parts over the dumped cases (the shapes, the

@@ -4,6 +4,7 @@
 // asserted.  No GPU, no HIP:
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 //       tools/wal_layout_check.cc leveldb-rs_amd/csrc/wal_layout.cc -o wal_layout_check && ./wal_layout_check
+// tests/test_host_checks.py builds it this way and runs it with the CPU suite.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>

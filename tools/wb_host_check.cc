@@ -4,6 +4,8 @@
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude
 //       tools/wb_host_check.cc leveldb-rs_amd/csrc/write_batch.cc -o wb_host_check && ./wb_host_check
 //
+// tests/test_host_checks.py builds it this way and runs it with the CPU suite.
+//
 // Every input is copied into a heap buffer of exactly its size, so a read one
 // byte past a rep is a heap-buffer-overflow.  Inputs: the reference's four
 // test cases (write_batch.rs:240-297), every truncation of a multi-op batch,
