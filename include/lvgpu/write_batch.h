@@ -158,6 +158,137 @@ int lv_write_batch_decode_device(const uint8_t *d_payload, size_t payload_bytes,
                                  size_t rec_cap, const lv_wb_decode_out *out, uint32_t flags,
                                  void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- The inverse: ops over a key/value arena to WriteBatch records ----
+ *
+ * What a writer does before it logs a commit group (DBImpl::Write upstream):
+ * WriteBatch::put / delete per op (write_batch.rs:64-78 over coding.rs'
+ * encode_length_prefixed_slice), WriteBatchInternal::set_sequence with
+ * last_sequence + 1, and WriteBatchInternal::append over the group's batches
+ * (write_batch.rs:131-161).  The reps come out end to end in d_out with the
+ * (d_rec_off, d_rec_len) arrays lv_wal_encode_device and
+ * lv_write_batch_decode_device take, and with the op table over d_out that
+ * lv_memtable_build_device takes: the log append and the memtable insert of a
+ * commit run from one encode.
+ *
+ * Inputs.  Record r, r < *d_records, is the ops d_ops[d_rec_op[r] ..
+ * d_rec_op[r + 1]): the bounds array lv_write_batch_decode_device writes,
+ * *d_records + 1 entries; d_rec_op[0] need not be 0.  Of an op the call reads
+ * tag & 0xFF (the type; the other 56 bits are ignored, so a decoded op table
+ * feeds in as it is), key_off / key_len and, for a VALUE only, val_off /
+ * val_len: a DELETION's value fields are neither read nor checked.  Offsets
+ * are into d_src[0, src_bytes) at any alignment; extents may overlap or
+ * repeat.  d_records and d_upstream_status are read on the device in stream
+ * order; d_upstream_status may be NULL.
+ *
+ * Outputs, when status == 0.  With ops = d_rec_op[*d_records] - d_rec_op[0]:
+ *   d_out[0, out_bytes)  the reps end to end.  Record r with n_r ops is
+ *       fixed64 first_sequence + (d_rec_op[r] - d_rec_op[0]) (wrapping u64),
+ *       fixed32 n_r, then per op the type byte, varint32(key_len), the key and
+ *       for a VALUE varint32(val_len), the value.  A record with no ops is its
+ *       12-byte header (WriteBatch::new and set_sequence).  These are the
+ *       bytes put / delete calls in op order and set_sequence leave, and what
+ *       WriteBatchInternal::append leaves over any split of the record's ops
+ *       into batches.
+ *   d_rec_off[r], d_rec_len[r]  r < records: the rep's extent in d_out;
+ *       d_rec_off[r] is the sum of the earlier lengths.
+ *   d_ops_out[j]  j = i - d_rec_op[0] < ops, unless d_ops_out is NULL: the op
+ *       lv_write_batch_decode_device writes for that entry of d_out: tag =
+ *       ((first_sequence + j) << 8) | type (the record's sequence plus the
+ *       index in the record), key_off / val_off into d_out, a DELETION with
+ *       val_off = key_off + key_len and val_len = 0.  (d_out, out_bytes,
+ *       d_ops_out, &d_totals->ops) goes straight into lv_memtable_build_device.
+ *   *d_totals  always written.  records, ops, key_bytes, value_bytes (VALUE
+ *       ops only), out_bytes; last_sequence = first_sequence - 1 + ops,
+ *       wrapping (DBImpl::Write's last_sequence += count) -- with the ops this
+ *       struct reports, so first_sequence - 1 whenever ops is 0; bad_record and
+ *       bad_op = 2^64 - 1 unless a bit below sets them.
+ *
+ * All or nothing.  If a status bit is set, only *d_totals is written.  The
+ * bits are judged in this order and the first one raised ends the judging:
+ *   UPSTREAM    *d_upstream_status != 0: the totals of zero records.
+ *   REC_OVER    *d_records > rec_cap: records = *d_records, the sums 0.
+ *   BAD_BOUNDS  not (d_rec_op[r] <= d_rec_op[r + 1] <= op_cap) for some r:
+ *               bad_record = the lowest such r, records = *d_records, the
+ *               sums 0.  No op is read.
+ *   BAD_OP      an op of some record has a type above 1, a key extent outside
+ *               [0, src_bytes) or, for a VALUE, a value extent outside it (u64
+ *               arithmetic, nothing wraps): bad_op = the lowest such index
+ *               into d_ops, bad_record = its record, records = *d_records, the
+ *               sums 0.  No byte of d_src is read.
+ *   OUT_OVER    out_bytes > out_cap: every total is the true one, so the
+ *               caller can size and call again.  12 records + 11 ops +
+ *               key_bytes + value_bytes always suffices (a header; a type byte
+ *               and two varint32 of at most five bytes per op).
+ *
+ * Arguments.  Every argument is checked on the host before any device call
+ * (LV_ERR_INVALID, lv_last_error): NULL pointers (out, d_totals, d_records and
+ * d_rec_op always; d_src only with src_bytes == 0, d_ops only with op_cap ==
+ * 0, d_out only with out_cap == 0, d_rec_off / d_rec_len only with rec_cap ==
+ * 0; d_ops_out may be NULL, and then no op table is written), d_ops and
+ * d_ops_out 16-byte aligned, d_totals, d_rec_op, d_rec_off and d_rec_len
+ * 8-byte aligned, d_workspace 16-byte aligned and >=
+ * lv_write_batch_encode_workspace_bytes(rec_cap, op_cap) bytes (not shared
+ * with a call that may run concurrently), flags == 0 (no flag is defined yet),
+ * rec_cap <= 2^32 - 2, op_cap <= 2^30 -- a record's count is a fixed32, and
+ * with u32 lengths an op's entry is below 2^33 + 11 bytes, so no sum of sizes
+ * over 2^30 ops and 2^32 headers can leave u64 --, d_out[0, out_cap) must not
+ * overlap d_src, d_ops or d_ops_out, and d_ops_out must not overlap d_ops.
+ * Without a usable GPU a well-formed call fails with the runtime's error:
+ * there is no host fallback.
+ *
+ * Reads and writes.  Nothing is read outside d_rec_op[0 .. *d_records], the
+ * ops of the records and, once every op has been accepted, their extents of
+ * d_src; nothing is written outside d_out[0, out_bytes), the first `records`
+ * entries of d_rec_off / d_rec_len, d_ops_out[0, ops) and *d_totals, whatever
+ * the inputs say.
+ *
+ * Stream-ordered, no host synchronisation, staging or stream queries: one
+ * memset and five launches on `stream` (three when op_cap == 0), their grids
+ * sized by rec_cap and op_cap; threads beyond the device-resident counts do
+ * nothing.  A key or value is copied by one group of lanes however long it is
+ * (as in lv_sst_build_device): a single very long value is the call's serial
+ * worst case. */
+#define LV_WB_ENCODE_UPSTREAM    1u
+#define LV_WB_ENCODE_REC_OVER    2u
+#define LV_WB_ENCODE_BAD_BOUNDS  4u
+#define LV_WB_ENCODE_BAD_OP      8u
+#define LV_WB_ENCODE_OUT_OVER   16u
+
+typedef struct lv_wb_encode_totals {   /* device memory, 8-B aligned, always written */
+    uint64_t records, ops, key_bytes, value_bytes, out_bytes, last_sequence, status, bad_record, bad_op;
+} lv_wb_encode_totals;
+
+typedef struct lv_wb_encode_out {      /* device memory the caller owns */
+    uint8_t *d_out;  size_t out_cap;   /* any byte alignment */
+    uint64_t *d_rec_off, *d_rec_len;   /* rec_cap each: exactly what lv_write_batch_decode_device takes */
+    lv_wb_op *d_ops_out;               /* op_cap, 16-B aligned; may be NULL */
+    lv_wb_encode_totals *d_totals;
+} lv_wb_encode_out;
+
+size_t lv_write_batch_encode_workspace_bytes(size_t rec_cap, size_t op_cap);
+int lv_write_batch_encode_device(const uint8_t *d_src, size_t src_bytes,
+                                 const lv_wb_op *d_ops, size_t op_cap,
+                                 const uint64_t *d_rec_op, const uint64_t *d_records,
+                                 const uint64_t *d_upstream_status, size_t rec_cap,
+                                 uint64_t first_sequence, const lv_wb_encode_out *out,
+                                 uint32_t flags, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* The same on the host, serially (no GPU): the arrays are host memory and
+ * `records` is the caller's own count (rec_off / rec_len hold that many
+ * entries), so UPSTREAM and REC_OVER do not arise; the other bits are judged
+ * as above and 0 is returned with the status in *totals; LV_ERR_INVALID
+ * for a NULL totals, rec_op, src with src_bytes (but see sizing), ops with op_cap, rec_off /
+ * rec_len with records, out with out_cap, records > 2^32 - 2 or op_cap > 2^30.
+ * ops_out may be NULL.
+ * Sizing mode, out == NULL and out_cap == 0: rec_off, rec_len, ops_out and the
+ * totals are written as if the capacity sufficed, OUT_OVER is not raised, and
+ * src is only bounds-checked, never read (it may be NULL) -- the host arrays
+ * lv_wal_encode_device wants, without a round trip. */
+int lv_write_batch_encode_host(const uint8_t *src, size_t src_bytes, const lv_wb_op *ops, size_t op_cap,
+                               const uint64_t *rec_op, size_t records, uint64_t first_sequence,
+                               uint8_t *out, size_t out_cap, uint64_t *rec_off, uint64_t *rec_len,
+                               lv_wb_op *ops_out, lv_wb_encode_totals *totals);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,14 @@
 // lv_write_batch_iterate: WriteBatch::iterate with a MemTableInserter as its
 // Handler (write_batch.rs:92-122, :178-188), one rep at a time on the host.
 // The scalar twin of the device walk in write_batch.hip; host only, no GPU.
+// lv_write_batch_encode_host: the inverse, WriteBatch::put / delete /
+// set_sequence (write_batch.rs:57-78) over an op table, record after record;
+// the scalar twin of write_batch_encode.hip.
 #include "../../include/lvgpu/write_batch.h"
+
+#include <cstring>
+
+#include "../../include/lvgpu/crc32c.h"
 
 namespace {
 
@@ -72,4 +79,120 @@ extern "C" uint32_t lv_write_batch_iterate(const uint8_t *rep, size_t n, lv_wb_o
     if (found) *found = emitted;
     if (status == LV_WB_OK && emitted != cnt) status = LV_WB_WRONG_COUNT;  // write_batch.rs:117-119
     return status;
+}
+
+namespace {
+
+constexpr uint64_t kEncMaxRecords = 0xfffffffeull;
+constexpr uint64_t kEncMaxOps = 1ull << 30;
+
+// [off, off + len) lies inside [0, bytes).  All u64: nothing wraps.
+bool extent_ok(uint64_t off, uint64_t len, uint64_t bytes) { return off <= bytes && len <= bytes - off; }
+
+uint32_t varint_len(uint32_t v) {
+    uint32_t n = 1;
+    for (; v >= 128; v >>= 7) ++n;
+    return n;
+}
+
+// coding.rs' encode_varint_32 at out + at (out may be null: sizing); returns the bytes.
+uint32_t put_varint(uint8_t *out, uint64_t at, uint32_t v) {
+    uint32_t n = 0;
+    for (; v >= 128; v >>= 7, ++n)
+        if (out) out[at + n] = static_cast<uint8_t>(v | 0x80);
+    if (out) out[at + n] = static_cast<uint8_t>(v);
+    return n + 1;
+}
+
+}  // namespace
+
+extern "C" int lv_write_batch_encode_host(const uint8_t *src, size_t src_bytes, const lv_wb_op *ops, size_t op_cap,
+                                          const uint64_t *rec_op, size_t records, uint64_t first_sequence, uint8_t *out,
+                                          size_t out_cap, uint64_t *rec_off, uint64_t *rec_len, lv_wb_op *ops_out,
+                                          lv_wb_encode_totals *totals) {
+    const bool sizing = !out && !out_cap;  // src is then never read and may be null
+    if (!totals || !rec_op || (!src && src_bytes && !sizing) || (!ops && op_cap) || (!out && out_cap) ||
+        (records && (!rec_off || !rec_len)) || records > kEncMaxRecords || op_cap > kEncMaxOps)
+        return LV_ERR_INVALID;
+    lv_wb_encode_totals t{};
+    t.records = records;
+    t.last_sequence = first_sequence - 1;
+    t.bad_record = t.bad_op = ~0ull;
+    // the bounds, before any op is read
+    for (size_t r = 0; r < records; ++r)
+        if (!(rec_op[r] <= rec_op[r + 1] && rec_op[r + 1] <= op_cap)) {
+            t.status = LV_WB_ENCODE_BAD_BOUNDS;
+            t.bad_record = r;
+            *totals = t;
+            return 0;
+        }
+    const uint64_t base = records ? rec_op[0] : 0, nops = records ? rec_op[records] - base : 0;
+    // every op, before any byte of src is read
+    uint64_t kb = 0, vb = 0, bytes = static_cast<uint64_t>(LV_WB_HEADER_SIZE) * records;
+    for (size_t r = 0; r < records; ++r)
+        for (uint64_t i = rec_op[r]; i < rec_op[r + 1]; ++i) {
+            const lv_wb_op &o = ops[i];
+            const uint32_t type = static_cast<uint32_t>(o.tag & 0xff);
+            if (type > LV_WB_TYPE_VALUE || !extent_ok(o.key_off, o.key_len, src_bytes) ||
+                (type == LV_WB_TYPE_VALUE && !extent_ok(o.val_off, o.val_len, src_bytes))) {
+                t.status = LV_WB_ENCODE_BAD_OP;
+                t.bad_record = r;
+                t.bad_op = i;
+                *totals = t;
+                return 0;
+            }
+            kb += o.key_len;
+            bytes += 1 + varint_len(o.key_len) + static_cast<uint64_t>(o.key_len);
+            if (type == LV_WB_TYPE_VALUE) {
+                vb += o.val_len;
+                bytes += varint_len(o.val_len) + static_cast<uint64_t>(o.val_len);
+            }
+        }
+    t.ops = nops;
+    t.key_bytes = kb;
+    t.value_bytes = vb;
+    t.out_bytes = bytes;
+    t.last_sequence = first_sequence - 1 + nops;
+    if (!sizing && bytes > out_cap) {
+        t.status = LV_WB_ENCODE_OUT_OVER;
+        *totals = t;
+        return 0;
+    }
+    uint64_t at = 0;
+    for (size_t r = 0; r < records; ++r) {
+        const uint64_t begin = at, seq = first_sequence + (rec_op[r] - base);
+        const uint32_t count = static_cast<uint32_t>(rec_op[r + 1] - rec_op[r]);
+        if (out) {
+            for (int i = 0; i < 8; ++i) out[at + i] = static_cast<uint8_t>(seq >> (8 * i));
+            for (int i = 0; i < 4; ++i) out[at + 8 + i] = static_cast<uint8_t>(count >> (8 * i));
+        }
+        at += LV_WB_HEADER_SIZE;
+        for (uint64_t i = rec_op[r]; i < rec_op[r + 1]; ++i) {
+            const lv_wb_op &o = ops[i];
+            const uint32_t type = static_cast<uint32_t>(o.tag & 0xff);
+            lv_wb_op w;
+            w.tag = ((first_sequence + (i - base)) << 8) | type;
+            if (out) out[at] = static_cast<uint8_t>(type);
+            ++at;
+            at += put_varint(out, at, o.key_len);
+            w.key_off = at;
+            w.key_len = o.key_len;
+            if (out && o.key_len) std::memcpy(out + at, src + o.key_off, o.key_len);
+            at += o.key_len;
+            w.val_off = at;
+            w.val_len = 0;
+            if (type == LV_WB_TYPE_VALUE) {
+                at += put_varint(out, at, o.val_len);
+                w.val_off = at;
+                w.val_len = o.val_len;
+                if (out && o.val_len) std::memcpy(out + at, src + o.val_off, o.val_len);
+                at += o.val_len;
+            }
+            if (ops_out) ops_out[i - base] = w;
+        }
+        rec_off[r] = begin;
+        rec_len[r] = at - begin;
+    }
+    *totals = t;
+    return 0;
 }
