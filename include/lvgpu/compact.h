@@ -12,8 +12,9 @@
  * memtable quadruple at once: it writes a second order array that holds the
  * kept entries only, and the totals that go with it.  The result is again a
  * memtable quadruple, which lv_sst_build_device and lv_memtable_get_device take
- * as it is.  The merging iterator as a streaming object, several output files
- * and version edits are not part of this.
+ * as it is.  lv_compact_output_device (below) writes the kept entries as a run
+ * of output tables.  The merging iterator as a streaming object and version
+ * edits are not part of this.
  *
  * The contract: upstream's loop.  The input is (d_payload, payload_bytes,
  * d_ops, d_order, *d_mt_totals), what lv_memtable_build_device or
@@ -114,6 +115,7 @@
 #include <stdint.h>
 
 #include "memtable.h"
+#include "version.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -153,6 +155,167 @@ int lv_compact_filter_host(const uint8_t *payload, size_t payload_bytes, const l
                            const lv_compact_range *ranges, size_t n_ranges, const uint8_t *range_keys,
                            size_t range_keys_bytes, uint32_t *order_out, lv_mt_totals *mt_totals_out,
                            lv_compact_totals *totals, uint32_t flags);
+
+/* ---- lv_compact_output_device: a compaction's output as a run of tables ------
+ *
+ * Upstream's DoCompactionWork adds the kept entries to a TableBuilder and closes
+ * the output file as soon as builder->FileSize() >= MaxOutputFileSize() (2 MiB
+ * by default), opening the next one with the next entry.  This call writes
+ * every output table of a compaction into one arena in HBM, 16-byte aligned
+ * one behind the other, together with the lv_sst_table, lv_sst_bloom and
+ * lv_version_file record of each, which lv_version_open_device and
+ * lv_version_get_device take as they are (version.h).  The only host-side fact
+ * a caller then needs is the file count, which lv_version_open_device takes as
+ * a host value.
+ *
+ * The serial contract (lv_compact_output_host runs exactly this).  The input is
+ * the memtable quadruple as lv_sst_build_bloom_device takes it.  Walk
+ * e_i = d_ops[d_order[i]], i < d_mt_totals->entries:
+ *   1. if no file is open, open file k with a fresh TableBuilder (with bloom, a
+ *      fresh FilterBlockBuilder too);
+ *   2. add(e_i) by the rules of table.h;
+ *   3. if the file's flushed bytes, the sum of raw + 5 over its data blocks
+ *      written so far (upstream's FileSize()), are >= max_file_bytes: finish
+ *      the file (TableBuilder::finish) and close it;
+ *   4. at the end, finish an open file.
+ * max_file_bytes >= 1.  A cut falls directly behind an add that flushed a
+ * block, so every file holds at least one entry, there is no empty last file
+ * and files <= data_blocks.
+ *
+ * The slice rule.  The image of file k is byte for byte what
+ * lv_sst_build_bloom_host (without bloom: lv_sst_build_host) writes for the
+ * order slice d_order[first_entry, first_entry + entries), its handle pairs
+ * included: d_handles holds the pairs of file k from pair index first_handle =
+ * sum over j < k of (data_blocks_j + extra), the data blocks, then the filter
+ * block if there is one, then metaindex and index: extra = 3 with a filter and
+ * 2 without.  Offsets are relative to the file, so
+ * lv_sst_verify_blocks_device(d_arena + file_off, file_bytes, d_handles + 2
+ * first_handle, data_blocks + extra, ...) takes them as they are.  The caller
+ * provides room for block_cap + 3 files_cap pairs.  File k lies at file_off[k] =
+ * align16(file_off[k-1] + file_bytes[k-1]), file_off[0] = 0; the up to 15 bytes
+ * between two files are never written.
+ *
+ * Records, each defined by an existing twin over image k:
+ *   d_files[k]   {first_entry, entries, file_off, file_bytes, data_blocks,
+ *                first_handle, filter_keys (= entries with bloom, else 0), 0}.
+ *   d_tables[k]  what lv_sst_open_host writes.
+ *   d_blooms[k]  (d_blooms may be NULL) what lv_sst_bloom_open_host writes;
+ *                without bloom that is present = 0 and the why the open gives.
+ *   d_version_files[k]  (may be NULL: then no bound keys are written and
+ *                bound_bytes is 0) what lv_version_file_host writes for number =
+ *                first_number + k, the given level, file_off = images_off +
+ *                file_off[k], where images_off is the position of d_arena in the
+ *                caller's d_images buffer, and file_cap = file_bytes.  Both
+ *                bound keys, the internal keys of the file's first and last
+ *                entry, are appended behind *d_bound_used, smallest then
+ *                largest, file after file, and the cursor is advanced once by
+ *                bound_bytes.
+ * level must lie in [1, 6]: output files are in key order, which is those
+ * levels' order (level 0 is the flush's job).  The call does not judge whether
+ * neighbours are strictly ordered; lv_version_open_device does (an exact
+ * duplicate astride a cut is its UNSORTED).
+ *
+ * Statuses are bits, decided once before any byte of any output but *d_totals
+ * is written.  On any of them the arena, the handles, every record array and
+ * the bound keys are untouched and the cursor is not advanced; *d_totals
+ * reports the true entries, files, data_blocks, arena_bytes, handle_pairs
+ * (= data_blocks + extra files) and bound_bytes, so one retry suffices, except
+ * under NO_TABLE, where everything but status is 0.
+ *   NO_TABLE     as LV_SST_BUILD_NO_TABLE (table.h).
+ *   HANDLE_OVER  data_blocks > block_cap.
+ *   ARENA_OVER   arena_bytes > arena_cap.
+ *   BLOCK_LARGE  table.h's meaning, for any file's data, index or filter block.
+ *   FILES_OVER   files > files_cap.
+ *   BOUND_OVER   with d_version_files: *d_bound_used > bound_keys_cap or
+ *                bound_bytes do not fit behind it.
+ * An empty memtable gives files = 0, status 0 and writes nothing.  With status 0
+ * nothing at or beyond arena_bytes is written.  All sizes and positions are u64.
+ *
+ * lv_compact_output_arena_bound returns an arena_cap that always suffices when
+ * the ops' extents are disjoint (saturating at 2^64 - 1; 0 for op_cap == 0 or
+ * bad bloom options): lv_sst_build_bloom_file_bound's derivation (table.h) with
+ * the per-file terms taken n = op_cap times, there being at most n files.
+ * Without a filter the per-file terms are the metaindex block 13, the footer
+ * 48, the index's count and trailer 9, and 15 bytes of alignment: 2
+ * payload_bytes + 75 n + 85 n.  With one, add the filters n bpk / 8 + 9 n, the
+ * windows' offsets (payload_bytes + 36 n) / 512 over all files plus per file
+ * one more offset 4 and the rounding 1, the filter block's fixed part 10 and
+ * the metaindex entry 57: + 72 n.
+ *
+ * Worked example (tests/golden/compact_output_example.json).  Entries
+ * ("k", seq 1, "v") and ("m", seq 2, "w"), block_size 1 (every entry a block),
+ * restart_interval 16, no filter, max_file_bytes 1: two files.  File 0 is
+ * arena[0, 114), byte for byte table.h's one-entry example: its index key is
+ * short_successor("k" ...), the key itself.  File 1 is arena[128, 242), the
+ * same with "m", tag 2 and "w"; arena[114, 128) is never written.  d_handles =
+ * {0,21} {26,8} {39,22} {0,21} {26,8} {39,22}; first_handle = 0 and 3;
+ * bound keys "k" 01 01 00.. | "k" 01 01 00.. | "m" 01 02 00.. | "m" 01 02 00..
+ * (36 bytes).  The one-file build of the same two entries has "l" + MAXTAG as
+ * its first index key (shortest_separator(k, m)), so a build that cuts the
+ * index wrongly fails this example.
+ *
+ * Arguments, checked on the host before any device call (LV_ERR_INVALID,
+ * lv_last_error): lv_sst_build_bloom_device's NULL and alignment rules (bloom
+ * may be NULL: no filter; d_arena 16-byte aligned, NULL only with arena_cap ==
+ * 0; d_files and d_tables NULL only with files_cap == 0; d_bound_used, and
+ * d_bound_keys unless bound_keys_cap == 0, needed with d_version_files; every
+ * record array and d_bound_used 8-byte aligned), max_file_bytes != 0, level in
+ * [1, 6], files_cap <= LV_VERSION_MAX_FILES, first_number + files_cap must not
+ * wrap, flags == 0, d_workspace 16-byte aligned and >=
+ * lv_compact_output_workspace_bytes(op_cap, block_cap, files_cap) bytes, and no
+ * output range may overlap an input range or another output range.  Without a
+ * usable GPU a well-formed call fails with the runtime's error.
+ *
+ * Stream-ordered: a linear chain of kernel launches, no host synchronisation,
+ * staging, stream query or memset; the launch sequence and every grid depend
+ * only on op_cap, block_cap, files_cap, arena_cap, restart_interval and whether
+ * bloom is given; capturable into a HIP graph once the device has been
+ * initialised.  The block starts of the run are those of the one-file build
+ * (a block starts with an empty builder, and so does a file), so the call
+ * begins with lv_sst_build_device's chain; the file starts are a second greedy
+ * chain over blocks, fnext(b) a bounded binary search over the scan of raw + 5
+ * and the true starts marked by the same pointer doubling.  No workgroup waits
+ * on another, launches beyond the device-side counts return at once, and no
+ * lane loops over a count of entries, blocks or files. */
+typedef struct lv_compact_output_file {   /* 64 bytes, one per output file */
+    uint64_t first_entry, entries, file_off, file_bytes, data_blocks, first_handle, filter_keys, reserved;
+} lv_compact_output_file;
+typedef struct lv_compact_output_totals { /* device memory, 8-B aligned, always written */
+    uint64_t entries, files, data_blocks, arena_bytes, handle_pairs, bound_bytes, reserved, status;
+} lv_compact_output_totals;
+#define LV_COMPACT_OUT_NO_TABLE     1u
+#define LV_COMPACT_OUT_HANDLE_OVER  2u   /* data_blocks > block_cap */
+#define LV_COMPACT_OUT_ARENA_OVER   4u   /* arena_bytes > arena_cap */
+#define LV_COMPACT_OUT_BLOCK_LARGE  8u
+#define LV_COMPACT_OUT_FILES_OVER  16u   /* files > files_cap */
+#define LV_COMPACT_OUT_BOUND_OVER  32u   /* the bound keys do not fit behind the cursor */
+
+size_t lv_compact_output_workspace_bytes(size_t op_cap, size_t block_cap, size_t files_cap);
+uint64_t lv_compact_output_arena_bound(uint64_t payload_bytes, uint64_t op_cap, const lv_sst_build_options *opt,
+                                       const lv_sst_bloom_options *bloom);
+int lv_compact_output_device(const uint8_t *d_payload, size_t payload_bytes, const lv_wb_op *d_ops,
+                             const uint32_t *d_order, const lv_mt_totals *d_mt_totals, size_t op_cap,
+                             const lv_sst_build_options *opt, const lv_sst_bloom_options *bloom, uint64_t max_file_bytes,
+                             uint64_t first_number, uint32_t level, uint64_t images_off, uint8_t *d_arena,
+                             uint64_t arena_cap, uint64_t *d_handles, size_t block_cap, lv_compact_output_file *d_files,
+                             lv_sst_table *d_tables, lv_sst_bloom *d_blooms, lv_version_file *d_version_files,
+                             size_t files_cap, uint8_t *d_bound_keys, uint64_t bound_keys_cap, uint64_t *d_bound_used,
+                             lv_compact_output_totals *d_totals, uint32_t flags, void *d_workspace,
+                             size_t workspace_bytes, void *stream);
+/* The host twin (pure, no GPU): the serial loop above over host memory with a
+ * real builder per file; the records are read back from the images by
+ * lv_sst_open_host, lv_sst_bloom_open_host and lv_version_file_host.  The same
+ * statuses and outputs.  arena == NULL with arena_cap == 0 is a sizing pass:
+ * only *totals is written, and the capacities are not judged.  Returns 0, or
+ * LV_ERR_INVALID for what the device call refuses (alignment and overlap are
+ * not checked). */
+int lv_compact_output_host(const uint8_t *payload, size_t payload_bytes, const lv_wb_op *ops, const uint32_t *order,
+                           const lv_mt_totals *mt_totals, size_t op_cap, const lv_sst_build_options *opt,
+                           const lv_sst_bloom_options *bloom, uint64_t max_file_bytes, uint64_t first_number,
+                           uint32_t level, uint64_t images_off, uint8_t *arena, uint64_t arena_cap, uint64_t *handles,
+                           size_t block_cap, lv_compact_output_file *files, lv_sst_table *tables, lv_sst_bloom *blooms,
+                           lv_version_file *version_files, size_t files_cap, uint8_t *bound_keys,
+                           uint64_t bound_keys_cap, uint64_t *bound_used, lv_compact_output_totals *totals);
 
 #ifdef __cplusplus
 }

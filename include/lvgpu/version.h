@@ -26,8 +26,9 @@
  * (DBImpl::Get's first two steps: lv_memtable_get_device has the same query
  * arrays and status numbers); UpdateStats / allowed_seeks bookkeeping
  * (seek_file and files_read are what it needs); VersionEdit encode / decode;
- * the table cache; iterators and range reads; multi-file compaction output;
- * compression.
+ * the table cache; iterators and range reads; compression.  (A compaction's
+ * output as a run of tables with their records: lv_compact_output_device,
+ * compact.h.)
  *
  * ---- Data (all in device memory) --------------------------------------------
  *

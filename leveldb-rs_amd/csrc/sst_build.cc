@@ -12,6 +12,7 @@
 #include "../../include/lvgpu/crc32c.h"
 #include "../../include/lvgpu/table.h"
 #include "lvk/sst_read.h"
+#include "sst_build_host.h"
 
 namespace {
 
@@ -219,6 +220,9 @@ struct Run {
     const uint32_t *order;
     uint64_t n, block_size, interval;
     uint32_t bpk;  // 0: no filter policy
+    // one output file of a compaction (compact_output.cc): the walk ends with the
+    // add after which the flushed bytes reach max_file (0: no limit)
+    uint64_t max_file = 0;
 };
 
 IKey ikey(const Run &R, uint64_t i) {
@@ -234,8 +238,9 @@ IKey ikey(const Run &R, uint64_t i) {
 // from the sizing pass).  handles is NULL in a sizing pass; a write pass runs
 // only with data_blocks <= block_cap, so it has room for data_blocks + 2 pairs
 // (+ 3 with a filter policy: the filter block's comes before the metaindex's).
-void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, lv_sst_build_totals *t,
-          lv_sst_bloom_totals *bt) {
+// Returns the entries added: R.n unless R.max_file ended the walk.
+uint64_t walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, lv_sst_build_totals *t,
+              lv_sst_bloom_totals *bt) {
     uint64_t offset = 0, blocks = 0;
     bool large = false;
     Block index(out, index_at, 1);
@@ -244,6 +249,7 @@ void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, l
     uint64_t pend_off = 0, pend_size = 0;
     IKey last{};
     FilterBlock filter{R.bpk};
+    uint64_t added = 0;
     auto add_index = [&](const Sep &s) {
         IKey k;
         k.k = last.k;
@@ -290,7 +296,12 @@ void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, l
                 ++blocks;
                 pending = true;
                 data.emplace(out, offset, R.interval);
+                if (R.max_file && offset >= R.max_file) {  // DoCompactionWork closes the file here
+                    added = i + 1;
+                    break;
+                }
             }
+            added = i + 1;
         }
         if (!data->empty()) {
             write_block(*data);
@@ -299,7 +310,7 @@ void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, l
         }
     }
     t->data_blocks = blocks;
-    if (!R.n) return;  // no file
+    if (!R.n) return 0;  // no file
     uint64_t nh = blocks;  // the next handle pair
     uint8_t fh[LV_SST_BLOCK_HANDLE_MAX];
     size_t fhn = 0;
@@ -358,6 +369,7 @@ void walk(const Run &R, const Sink &out, uint64_t index_at, uint64_t *handles, l
         lv_sst_footer_encode(t->metaindex_offset, t->metaindex_size, t->index_offset, t->index_size, out.file + offset);
     t->file_bytes = offset + LV_SST_FOOTER_SIZE;
     if (large) t->status |= LV_SST_BUILD_BLOCK_LARGE;
+    return added;
 }
 
 bool extent_ok(uint64_t off, uint64_t len, uint64_t bytes) { return off <= bytes && len <= bytes - off; }
@@ -369,6 +381,22 @@ bool options_ok(const lv_sst_build_options *opt, uint64_t *bs, uint64_t *ri) {
 }
 
 }  // namespace
+
+uint64_t lvgpu_host::sst_build_prefix(const uint8_t *payload, const lv_wb_op *ops, const uint32_t *order, uint64_t n,
+                                      uint64_t block_size, uint64_t restart_interval, uint32_t bpk,
+                                      uint64_t max_file_bytes, uint8_t *file, uint64_t index_offset,
+                                      uint64_t *handles, lv_sst_build_totals *totals,
+                                      lv_sst_bloom_totals *bloom_totals) {
+    Run R{payload, ops, order, n, block_size, restart_interval, bpk};
+    R.max_file = max_file_bytes;
+    lv_sst_build_totals t{};
+    lv_sst_bloom_totals bt{};
+    const uint64_t added = walk(R, Sink{file}, file ? index_offset : 0, file ? handles : nullptr, &t, &bt);
+    t.entries = added;
+    *totals = t;
+    *bloom_totals = bt;
+    return added;
+}
 
 extern "C" {
 

@@ -85,109 +85,17 @@
 #include "lv_internal.h"
 #include "lvh.h"
 #include "lvk/knobs.h"
+#include "lvk/sst_build.h"
 #include "lvk/sst_read.h"
 #include "lvk/stage.h"
 
 namespace lvk {
 
-constexpr uint32_t kSbTile = LVK_SB_TILE;            // entries per scan tile
-constexpr uint32_t kSbWaveCopy = LVK_SB_WAVE_COPY;   // bytes from which a copy is the wave's
-constexpr uint32_t kSbCopyLanes = LVK_SB_COPY_LANES; // lanes of a wave that share one such copy
-constexpr uint32_t kSbThreads = 256;
-constexpr uint32_t kSbPer = kSbTile / kSbThreads;
-constexpr uint32_t kSbMaxR = LV_SST_MAX_RESTART_INTERVAL;
-constexpr uint64_t kSbLarge = 0xffffffffull;  // raw sizes from here on: sst_in_range refuses them
-constexpr uint32_t kSbBloomLds = 2048;        // bytes of filter bits a wave holds in LDS (1,638 keys at 10 bits per key)
-constexpr uint32_t kSbBloomName = sizeof(LV_SST_BLOOM_NAME) - 1;
-static_assert(kSbBloomName == 34 && kSbBloomLds % 4 == 0, "the metaindex key; whole LDS words");
-static_assert(kSbTile % kSbThreads == 0 && kSbTile >= kSbMaxR, "a tile holds every residue of a restart interval");
-static_assert(kSbTile * 16 <= 65536, "two u64 scan arrays fit the LDS a workgroup may declare");
-static_assert(kSbWaveCopy >= 16, "a wave copy has at least one granule");
-static_assert(kSbCopyLanes >= 16 && 64 % kSbCopyLanes == 0, "a copy's lanes cover a ragged head or tail of 15 bytes");
-
-struct SbHead {  // workspace, zeroed by sb_init
-    uint32_t bad, large, go, pad;
-    unsigned long long nblocks, data_bytes, idx_bytes, meta_off, index_off, index_size;
-};
-
-struct SbBloomHead {  // workspace, zeroed by sb_init
-    unsigned long long filt_bytes, filter_off, filter_size, filters, meta_size;
-    unsigned long long big;  // some filter is beyond kSbBloomLds bytes: sb_bloom_big has work
-    unsigned long long pad[2];
-};
-
-struct SbArgs {
-    const uint8_t *payload;
-    uint64_t payload_bytes;
-    const lv_wb_op *ops;
-    const uint32_t *order;
-    const lv_mt_totals *mt;
-    uint64_t op_cap;
-    uint32_t bs, R;
-    uint8_t *file;
-    uint64_t file_cap;
-    uint64_t *handles;
-    uint64_t block_cap;
-    lv_sst_build_totals *totals;
-    // workspace
-    SbHead *head;
-    uint64_t *shared;        // [cap] common prefix with the entry before, over internal-key bytes
-    uint64_t *Pl, *Sl;       // [cap] tile-local inclusive scans
-    uint64_t *cP, *cS;       // [tiles], [tiles * R]: the tiles' sums, then their exclusive scans
-    uint32_t *nxt, *J[2];    // [cap] next(s); the doubling's jump arrays
-    uint8_t *F;              // [cap] block-start flags
-    uint64_t *Cl, *Bl, *Il;  // [cap] tile-local scans: block count, file bytes, index bytes
-    uint64_t *cC, *cB, *cI;  // [tiles]
-    uint32_t *blk_start;     // [block_cap]
-    uint64_t *wsh;           // [2 (block_cap + 2)] the handles the seal reads
-    uint64_t *idx_off;       // [1] the index block as a one-buffer batch of the offsets API:
-    uint32_t *idx_len;       // [1] contents || type
-    uint32_t *idx_crc;       // [1] its masked crc
-    // lv_sst_build_bloom_device (bpk != 0; table.h, "Bloom filter blocks").  The
-    // arrays are by block id and hold op_cap entries: a table has no more
-    // blocks than entries, whatever block_cap is.  With a filter the batch
-    // above has two buffers, the index block and the filter block, and wsh
-    // 2 (block_cap + 3) words.
-    uint32_t bpk;
-    lv_sst_bloom_totals *btotals;
-    SbBloomHead *bh;
-    uint64_t *boff;          // [cap] the block's file offset
-    uint32_t *bstart;        // [cap] its first entry
-    uint32_t *Fn;            // [cap] the keys of the window it is the first block of, or 0
-    uint64_t *Fl;            // [cap] tile-local exclusive scan of the filters' bytes
-    uint64_t *cF;            // [tiles]
-};
-
-// The entries, or 0 when there is no table to read.
-__device__ __forceinline__ uint64_t sb_entries(const SbArgs &A) {
-    const uint64_t n = A.mt->entries;
-    return (A.mt->status || n > A.op_cap) ? 0 : n;
-}
-
-__device__ __forceinline__ uint32_t sb_varint_len(uint64_t v) {
-    uint32_t n = 1;
-    while (v >= 128) {
-        v >>= 7;
-        ++n;
-    }
-    return n;
-}
-
-__device__ __forceinline__ uint8_t *sb_put_varint(uint8_t *p, uint64_t v) {
-    while (v >= 128) {
-        *p++ = static_cast<uint8_t>(v | 0x80);
-        v >>= 7;
-    }
-    *p++ = static_cast<uint8_t>(v);
-    return p;
-}
-
-__device__ __forceinline__ void sb_put_fixed32(uint8_t *p, uint32_t v) {
-    p[0] = static_cast<uint8_t>(v);
-    p[1] = static_cast<uint8_t>(v >> 8);
-    p[2] = static_cast<uint8_t>(v >> 16);
-    p[3] = static_cast<uint8_t>(v >> 24);
-}
+// (The call's arguments, the size algebra, the separator, the index entry and
+// the body of the entry emit are lvk/sst_build.h's: compact_output.hip shares
+// them.)
+constexpr uint32_t kSbBloomLds = 2048;  // bytes of filter bits a wave holds in LDS (1,638 keys at 10 bits per key)
+static_assert(kSbBloomLds % 4 == 0, "whole LDS words");
 
 // Byte i of the internal key (user key at k, ulen bytes, then the tag LE).
 __device__ __forceinline__ uint32_t sb_ikey_at(const uint8_t *k, uint64_t ulen, uint64_t tag, uint64_t i) {
@@ -219,29 +127,13 @@ __device__ __forceinline__ uint64_t sb_shared(const SbArgs &A, const lv_wb_op &p
     return s;
 }
 
-// The global scans from the tile-local ones and the scanned carries.
-__device__ __forceinline__ uint64_t sb_P(const SbArgs &A, uint64_t i) { return A.Pl[i] + A.cP[i / kSbTile]; }
-__device__ __forceinline__ uint64_t sb_S(const SbArgs &A, uint64_t i) {
-    return A.Sl[i] + A.cS[(i / kSbTile) * A.R + i % A.R];
-}
-// len(buffer) of the block that starts at s after entry e >= s, and its restarts.
-__device__ __forceinline__ uint64_t sb_buffer(const SbArgs &A, uint64_t s, uint64_t e, uint64_t *restarts) {
-    const uint64_t k = (e - s) / A.R, last = s + k * A.R;
-    *restarts = k + 1;
-    return sb_P(A, e) - (s ? sb_P(A, s - 1) : 0) + sb_S(A, last) - (s >= A.R ? sb_S(A, s - A.R) : 0);
-}
-__device__ __forceinline__ uint64_t sb_estimate(const SbArgs &A, uint64_t s, uint64_t e) {
-    uint64_t r;
-    const uint64_t b = sb_buffer(A, s, e, &r);
-    return b + 4 * r + 4;
-}
-
 // Kernel 0 (one thread): the head.  A kernel, not a memset: the call is a
 // chain of kernel launches only, which is what a captured graph replays.
 __global__ void sb_init(const SbArgs A) {
     SbHead h{};
     *A.head = h;
     if (A.bpk) *A.bh = SbBloomHead{};
+    if (A.mf) *A.ch = CoHead{};
 }
 
 // Kernel 1: sizes and the tile-local scans of P and S.
@@ -305,18 +197,36 @@ __global__ __launch_bounds__(kSbThreads) void sb_sizes(const SbArgs A) {
 // Kernel 2: the exclusive scan over the tiles of column c, in place; one wave
 // per column.  Column c is col[c + t * stride], t < tiles; its sum goes to
 // total[c] when total is not null.  which: 0 = {P, S residues} (cP is column
-// R), 1 = {block count, file bytes}, 2 = {index bytes}, 3 = {filter bytes}.
+// R), 1 = {block count, file bytes}, 2 = {index bytes}, 3 = {filter bytes};
+// for several files (compact_output.hip) 4 = {file count}, 5 = {index bytes,
+// filter bytes}, both by block id, and 6 = {file bytes, bound bytes, windows}
+// by file.
 __global__ __launch_bounds__(kSbThreads) void sb_carry(const SbArgs A, uint32_t which) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t c = blockIdx.x * (kSbThreads / 64) + (threadIdx.x >> 6);
     const uint64_t n = sb_entries(A);
     if (!n || A.head->bad) return;
-    // (the filters' column is by block id)
-    const uint64_t tiles = ((which == 3 ? static_cast<uint64_t>(A.head->nblocks) : n) + kSbTile - 1) / kSbTile;
+    // (the filters' column is by block id, as 4 and 5 are; 6 is by file)
+    const uint64_t units = which == 6 ? static_cast<uint64_t>(A.ch->nfiles)
+                           : which >= 3 ? static_cast<uint64_t>(A.head->nblocks)
+                                        : n;
+    const uint64_t tiles = (units + kSbTile - 1) / kSbTile;
     uint64_t *col;
     uint64_t stride = 1;
     unsigned long long *total = nullptr;
-    if (which == 0) {
+    if (which == 4) {  // several files: the file count over the blocks
+        if (c > 0) return;
+        col = A.cK;
+        total = &A.ch->nfiles;
+    } else if (which == 5) {  // ... the index bytes and the filters' bytes over the blocks
+        if (c > (A.bpk ? 1u : 0u)) return;
+        col = c ? A.cF : A.cI;
+        total = c ? &A.bh->filt_bytes : nullptr;  // (a file's index bytes are differences of the scan)
+    } else if (which == 6) {  // ... the files' bytes, bound bytes and windows
+        if (c > 2) return;
+        col = c == 0 ? A.cA : c == 1 ? A.cU : A.cW;
+        total = c == 0 ? &A.ch->arena_al : c == 1 ? &A.ch->bound_bytes : &A.ch->windows;
+    } else if (which == 0) {
         if (c > A.R) return;
         col = c == A.R ? A.cP : A.cS + c;
         stride = c == A.R ? 1 : A.R;
@@ -362,12 +272,8 @@ __global__ __launch_bounds__(kSbThreads) void sb_next(const SbArgs A) {
 __global__ __launch_bounds__(kSbThreads) void sb_reach(const SbArgs A, uint32_t pass) {
     const uint64_t n = sb_entries(A);
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kSbThreads + threadIdx.x;
-    if (i >= n || A.head->bad || (1ull << pass) >= n) return;
-    const uint32_t *src = pass == 0 ? A.nxt : A.J[(pass - 1) & 1u];
-    uint32_t *dst = A.J[pass & 1u];
-    const uint32_t j = src[i];
-    if (j < n && A.F[i]) A.F[j] = 1;
-    dst[i] = j < n ? src[j] : static_cast<uint32_t>(n);
+    if (A.head->bad) return;
+    sb_reach_pass(n, i, pass, A.nxt, A.J, A.F);
 }
 
 // Kernel 5: per block start its raw size; tile scans of the count and the bytes.
@@ -410,45 +316,6 @@ __global__ __launch_bounds__(kSbThreads) void sb_layout(const SbArgs A) {
     }
 }
 
-// The index key of the block whose last entry is e (op o): `copy` bytes of
-// its user key, then (bump) the byte after them plus one and MAXTAG, or its
-// own tag.  shortest_separator against entry e + 1, short_successor at the end.
-struct SbSep {
-    uint64_t copy;
-    bool bump;
-};
-__device__ __forceinline__ SbSep sb_separator(const SbArgs &A, uint64_t e, uint64_t n, const lv_wb_op &o) {
-    const uint8_t *ka = A.payload + o.key_off;
-    const uint64_t la = o.key_len;
-    if (e + 1 < n) {
-        const lv_wb_op b = load_op(A.ops + A.order[e + 1]);
-        const uint64_t lb = b.key_len, m = la < lb ? la : lb;
-        uint64_t d = A.shared[e + 1];  // over internal keys: the user keys' is no longer than either
-        if (d > m) d = m;
-        if (d >= m) return SbSep{la, false};
-        const uint32_t c = ka[d];
-        if (c < 0xffu && c + 1 < A.payload[b.key_off + d]) return SbSep{d, true};
-        return SbSep{la, false};
-    }
-    uint64_t i = 0;
-    while (i < la && ka[i] == 0xffu) ++i;
-    if (i >= la || i + 1 >= la) return SbSep{la, false};
-    return SbSep{i, true};
-}
-
-struct SbIndexEntry {
-    uint64_t klen, hlen, size;
-    SbSep sep;
-};
-__device__ __forceinline__ SbIndexEntry sb_index_entry(const SbArgs &A, uint64_t e, uint64_t n, const lv_wb_op &o,
-                                                       uint64_t off, uint64_t raw) {
-    SbIndexEntry x;
-    x.sep = sb_separator(A, e, n, o);
-    x.klen = x.sep.copy + (x.sep.bump ? 1 : 0) + 8;
-    x.hlen = sb_varint_len(off) + sb_varint_len(raw);
-    x.size = 1 + sb_varint_len(x.klen) + sb_varint_len(x.hlen) + x.klen + x.hlen;
-    return x;
-}
 
 // Kernel 6: per block start its id, offset and handle; the index entry's size
 // and its tile scan.
@@ -476,7 +343,7 @@ __global__ __launch_bounds__(kSbThreads) void sb_index(const SbArgs A) {
                 A.boff[b] = off;
                 A.bstart[b] = static_cast<uint32_t>(s);
             }
-            v = sb_index_entry(A, e, n, load_op(A.ops + A.order[e]), off, raw).size;
+            v = sb_index_entry(A, e, e + 1 >= n, load_op(A.ops + A.order[e]), off, raw).size;
         }
         s_i[j] = v;
     }
@@ -545,6 +412,21 @@ __global__ void sb_plan(const SbArgs A) {
     if (A.bpk) *A.btotals = t.status || !n ? lv_sst_bloom_totals{} : bt;
 }
 
+// One file at A.file: a block's place is its handle in the workspace, and the
+// index entries are scanned by entry position.
+struct SbOneFile {
+    const SbArgs &A;
+    __device__ __forceinline__ SbBlockAt block(uint64_t i) const {
+        const uint64_t b = A.Cl[i] + A.cC[i / kSbTile] - 1;  // < block_cap: the plan checked
+        return SbBlockAt{A.blk_start[b], A.wsh[2 * b], A.wsh[2 * b], A.wsh[2 * b + 1]};
+    }
+    __device__ __forceinline__ SbIndexAt index(uint64_t i, const SbBlockAt &B) const {
+        const uint64_t n = sb_entries(A);
+        return SbIndexAt{A.file + A.head->index_off, A.head->idx_bytes, A.Cl[i] + A.cC[i / kSbTile] - 1,
+                         A.Il[i] + A.cI[i / kSbTile], static_cast<uint64_t>(A.nxt[B.s]) >= n};
+    }
+};
+
 // Kernel 8: the entries, the restart arrays, the index entries.  Every lane of
 // a wave stays to the end: the long copies are the wave's.
 __global__ __launch_bounds__(kSbThreads) void sb_emit(const SbArgs A) {
@@ -553,67 +435,7 @@ __global__ __launch_bounds__(kSbThreads) void sb_emit(const SbArgs A) {
     const uint64_t n = sb_entries(A);
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kSbThreads + threadIdx.x;
     if (static_cast<uint64_t>(blockIdx.x) * kSbThreads >= n) return;
-    const bool on = i < n;
-    // three copy jobs per lane: key suffix, value, index key
-    uint8_t *kd = nullptr, *vd = nullptr, *xd = nullptr;
-    const uint8_t *ks = nullptr, *vs = nullptr, *xs = nullptr;
-    uint64_t kn = 0, vn = 0, xn = 0;
-    if (on) {
-        const lv_wb_op o = load_op(A.ops + A.order[i]);
-        const uint64_t b = A.Cl[i] + A.cC[i / kSbTile] - 1;  // < block_cap: the plan checked
-        const uint64_t s = A.blk_start[b], boff = A.wsh[2 * b], raw = A.wsh[2 * b + 1];
-        const bool restart = (i - s) % A.R == 0;
-        uint64_t r;
-        const uint64_t rel = i > s ? sb_buffer(A, s, i - 1, &r) : 0;
-        const uint64_t ulen = o.key_len, klen = ulen + 8, sh = restart ? 0 : A.shared[i];
-        uint8_t *p = A.file + boff + rel;
-        p = sb_put_varint(p, sh);
-        p = sb_put_varint(p, klen - sh);
-        p = sb_put_varint(p, o.val_len);
-        if (sh < ulen) {
-            kd = p;
-            ks = A.payload + o.key_off + sh;
-            kn = ulen - sh;
-            p += kn;
-        }
-        for (uint32_t t = sh > ulen ? static_cast<uint32_t>(sh - ulen) : 0; t < 8; ++t)
-            *p++ = static_cast<uint8_t>(o.tag >> (8 * t));
-        vd = p;
-        vs = A.payload + o.val_off;
-        vn = o.val_len;
-        const uint64_t cnt = static_cast<uint64_t>(A.nxt[s]) - s, nrest = (cnt + A.R - 1) / A.R;
-        uint8_t *arr = A.file + boff + raw - 4 - 4 * nrest;  // the block's restart array
-        if (restart) sb_put_fixed32(arr + 4 * ((i - s) / A.R), static_cast<uint32_t>(rel));
-        if (i == s) {
-            sb_put_fixed32(arr + 4 * nrest, static_cast<uint32_t>(nrest));
-            // the block's index entry: shared = 0, the key, the handle
-            const uint64_t e = s + cnt - 1;
-            const lv_wb_op le = load_op(A.ops + A.order[e]);
-            const SbIndexEntry x = sb_index_entry(A, e, n, le, boff, raw);
-            const uint64_t at = A.Il[i] + A.cI[i / kSbTile] - x.size;
-            uint8_t *ix = A.file + A.head->index_off;
-            sb_put_fixed32(ix + A.head->idx_bytes + 4 * b, static_cast<uint32_t>(at));
-            uint8_t *q = ix + at;
-            q = sb_put_varint(q, 0);
-            q = sb_put_varint(q, x.klen);
-            q = sb_put_varint(q, x.hlen);
-            xd = q;
-            xs = A.payload + le.key_off;
-            xn = x.sep.copy;
-            q += xn;
-            uint64_t tg = le.tag;
-            if (x.sep.bump) {
-                *q++ = static_cast<uint8_t>(xs[xn] + 1);
-                tg = (LV_MT_MAX_SEQUENCE << 8) | 1u;  // MAXTAG
-            }
-            for (uint32_t t = 0; t < 8; ++t) *q++ = static_cast<uint8_t>(tg >> (8 * t));
-            q = sb_put_varint(q, boff);
-            q = sb_put_varint(q, raw);
-        }
-    }
-    group_copy<kSbCopyLanes, kSbWaveCopy>(kd, ks, kn, lane);
-    group_copy<kSbCopyLanes, kSbWaveCopy>(vd, vs, vn, lane);
-    if (__ballot(xn != 0)) group_copy<kSbCopyLanes, kSbWaveCopy>(xd, xs, xn, lane);
+    sb_emit_entry(A, i, i < n, lane, SbOneFile{A});
 }
 
 // Kernel 9: d_handles and the workspace copy's padding; one thread writes the
@@ -692,15 +514,6 @@ __global__ void sb_index_trailer(const SbArgs A) {
 
 // ---- the filter block (lv_sst_build_bloom_device) ----
 
-// Bytes of the Bloom filter over `keys` keys, without its k byte.
-__device__ __forceinline__ uint64_t sb_bloom_bytes(uint64_t keys, uint32_t bpk) {
-    const uint64_t want = keys * bpk;  // keys < 2^32, bpk <= 64
-    return ((want < 64 ? 64 : want) + 7) / 8;
-}
-__device__ __forceinline__ uint32_t sb_bloom_k(uint32_t bpk) {
-    const uint32_t k = bpk * 69 / 100;
-    return k < 1 ? 1 : k > 30 ? 30 : k;
-}
 
 // Kernel B1, a lane per data block (by id, after sb_index and the layout's
 // carry): whether it is the first block of its window, then the keys of the
@@ -780,12 +593,11 @@ __global__ __launch_bounds__(kSbThreads) void sb_bloom_emit(const SbArgs A) {
     const uint64_t nb = A.head->nblocks, step = static_cast<uint64_t>(gridDim.x) * (kSbThreads / 64);
     const uint32_t k = sb_bloom_k(A.bpk);
     uint32_t *bits = s_bits[wave];
-    uint8_t *fbase = A.file + A.bh->filter_off;
     for (uint64_t b = static_cast<uint64_t>(blockIdx.x) * (kSbThreads / 64) + wave; b < nb; b += step) {  // wave-uniform
         const uint32_t keys = A.Fn[b];
         if (!keys) continue;
         const uint64_t bytes = sb_bloom_bytes(keys, A.bpk);
-        uint8_t *dst = fbase + A.Fl[b] + A.cF[b / kSbTile];
+        uint8_t *dst = sb_filter_at(A, b);
         if (bytes > kSbBloomLds) {
             const uint64_t head = (4u - (reinterpret_cast<uintptr_t>(dst) & 3u)) & 3u;  // < 8 <= bytes
             const uint64_t words = (bytes - head) / 4, tail = (bytes - head) % 4;
@@ -793,6 +605,7 @@ __global__ __launch_bounds__(kSbThreads) void sb_bloom_emit(const SbArgs A) {
             for (uint64_t g = lane; g < words; g += 64) *reinterpret_cast<uint32_t *>(dst + head + 4 * g) = 0;
             if (lane < tail) dst[head + 4 * words + lane] = 0;
             if (lane == 0) dst[bytes] = static_cast<uint8_t>(k);
+            if (A.mf && lane == 0) atomicOr(&A.bh->big, 1ull);  // (one file: sb_bloom_sizes said so before the plan)
             continue;
         }
         const uint32_t nbytes = static_cast<uint32_t>(bytes), nbits = nbytes * 8;
@@ -830,13 +643,12 @@ __global__ __launch_bounds__(kSbThreads) void sb_bloom_big(const SbArgs A) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t nb = A.head->nblocks, step = static_cast<uint64_t>(gridDim.x) * (kSbThreads / 64);
     const uint32_t k = sb_bloom_k(A.bpk);
-    uint8_t *fbase = A.file + A.bh->filter_off;
     for (uint64_t b = static_cast<uint64_t>(blockIdx.x) * (kSbThreads / 64) + wave; b < nb; b += step) {
         const uint32_t keys = A.Fn[b];
         if (!keys) continue;
         const uint64_t bytes = sb_bloom_bytes(keys, A.bpk), nbits = bytes * 8;
         if (bytes <= kSbBloomLds) continue;
-        const uintptr_t dst = reinterpret_cast<uintptr_t>(fbase + A.Fl[b] + A.cF[b / kSbTile]);
+        const uintptr_t dst = reinterpret_cast<uintptr_t>(sb_filter_at(A, b));
         const uint64_t s = A.bstart[b];
         for (uint32_t i = lane; i < keys; i += 64) {
             const lv_wb_op o = load_op(A.ops + A.order[s + i]);
@@ -859,8 +671,18 @@ __global__ __launch_bounds__(kSbThreads) void sb_bloom_big(const SbArgs A) {
 // window's filter is zero bytes); with no such block every filter lies before.
 __global__ __launch_bounds__(kSbThreads) void sb_bloom_offsets(const SbArgs A) {
     if (!A.head->go) return;
-    const uint64_t nb = A.head->nblocks, F = A.bh->filters, total = A.bh->filt_bytes;
     const uint64_t step = static_cast<uint64_t>(gridDim.x) * kSbThreads;
+    if (A.mf) {  // several files: the windows are numbered file after file
+        const uint64_t W = A.ch->windows;
+        for (uint64_t f = static_cast<uint64_t>(blockIdx.x) * kSbThreads + threadIdx.x; f < W; f += step) {
+            uint8_t *slot;
+            uint32_t value;
+            co_window(A, f, &slot, &value);
+            sb_put_fixed32(slot, value);
+        }
+        return;
+    }
+    const uint64_t nb = A.head->nblocks, F = A.bh->filters, total = A.bh->filt_bytes;
     uint8_t *arr = A.file + A.bh->filter_off + total;
     for (uint64_t f = static_cast<uint64_t>(blockIdx.x) * kSbThreads + threadIdx.x; f < F; f += step) {
         const uint64_t lim = f << LV_SST_FILTER_BASE_LG;
