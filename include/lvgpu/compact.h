@@ -13,8 +13,11 @@
  * kept entries only, and the totals that go with it.  The result is again a
  * memtable quadruple, which lv_sst_build_device and lv_memtable_get_device take
  * as it is.  lv_compact_output_device (below) writes the kept entries as a run
- * of output tables.  The merging iterator as a streaming object and version
- * edits are not part of this.
+ * of output tables, and lv_memtable_range_device (memtable.h) reads ranges
+ * over either quadruple as DBIter would.  Range reads over a version go
+ * through scans and a memtable build for now; reading ranges straight from
+ * table images, reverse iteration (Prev, SeekToLast), the merging iterator as
+ * a streaming object and version edits are not part of this.
  *
  * The contract: upstream's loop.  The input is (d_payload, payload_bytes,
  * d_ops, d_order, *d_mt_totals), what lv_memtable_build_device or

@@ -26,9 +26,14 @@
  * (DBImpl::Get's first two steps: lv_memtable_get_device has the same query
  * arrays and status numbers); UpdateStats / allowed_seeks bookkeeping
  * (seek_file and files_read are what it needs); VersionEdit encode / decode;
- * the table cache; iterators and range reads; compression.  (A compaction's
- * output as a run of tables with their records: lv_compact_output_device,
- * compact.h.)
+ * the table cache; iterators and range reads over a version; compression.
+ * (A compaction's output as a run of tables with their records:
+ * lv_compact_output_device, compact.h.  Range reads: lv_memtable_range_device,
+ * memtable.h, is DBIter's forward walk over a sorted memtable quadruple; for
+ * now a version's range goes through lv_sst_scan_device per table, appended,
+ * and lv_memtable_build_device, the merged view, and is read there.  Reading
+ * ranges straight from table images, reverse iteration (Prev, SeekToLast) and
+ * a streaming merging iterator stay out of scope.)
  *
  * ---- Data (all in device memory) --------------------------------------------
  *

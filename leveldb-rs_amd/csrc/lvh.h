@@ -1,7 +1,7 @@
 // Host internals shared by the product library's HIP translation units
 // (blocks.hip, sort.hip, classes.hip, sst.hip, context.hip; the WAL stages
 // wal_scan.hip, wal_encode.hip, wal_decode.hip; the op-table stages
-// write_batch.hip, write_batch_encode.hip, memtable.hip, sst_build.hip, sst_get.hip, sst_scan.hip,
+// write_batch.hip, write_batch_encode.hip, memtable.hip, memtable_range.hip, sst_build.hip, sst_get.hip, sst_scan.hip,
 // compact.hip, version.hip):
 // lv_last_error plumbing, the per-device context (table images, sort
 // workspaces, piece matrices, host-path staging), the argument checks and

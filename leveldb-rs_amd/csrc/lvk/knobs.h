@@ -39,7 +39,8 @@
     defined(LVK_SS_TILE) || \
     defined(LVK_SS_WAVE_COPY) || \
     defined(LVK_SS_COPY_LANES) || \
-    defined(LVK_CF_TILE))
+    defined(LVK_CF_TILE) || \
+    defined(LVK_MR_SEEK_FAN))
 #error "LVK_* kernel switches select untested code paths; only experiment variants (LVK_EXPERIMENT_BUILD, tools/build_variant.sh) may set them"
 #endif
 
@@ -120,4 +121,7 @@
 #endif
 #ifndef LVK_CF_TILE  // compaction filter: entries per scan tile of the flag kernel; a multiple of 256, at most 32,768 (the tile's four counts share one scanned word)
 #define LVK_CF_TILE 1024
+#endif
+#ifndef LVK_MR_SEEK_FAN  // memtable range: pivots a wave probes per search step, 1..64 (r18, 2^20 seeks over 512 K entries at limit 16: 8 is 2.0x faster than 1, the binary search, and 1.6x faster than 64; 16 is level with 8; profiles/r18/mt_range/)
+#define LVK_MR_SEEK_FAN 8
 #endif

@@ -1,6 +1,6 @@
 // Device primitives shared by the pipeline stages (lvk/stage.h): WriteBatch
 // decode (write_batch.hip) and encode (write_batch_encode.hip), memtable build
-// and get (memtable.hip), SSTable
+// and get (memtable.hip) and range reads (memtable_range.hip), SSTable
 // build (sst_build.hip), get (sst_get.hip) and scan (sst_scan.hip), the
 // compaction filter (compact.hip).
 //

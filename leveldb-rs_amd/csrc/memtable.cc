@@ -1,8 +1,9 @@
 // The host twins of memtable.hip (include/lvgpu/memtable.h): the comparator of
 // internal keys (dbformat.rs:153-170), the op table sorted into memtable
-// order with std::sort, and MemTable::get (memtable.rs:105-143) over such a
-// table.  Host only, no GPU; the model-independent check of the device path
-// and the baseline of tools/bench_memtable.py.
+// order with std::sort, MemTable::get (memtable.rs:105-143) and DBIter's
+// forward walk (upstream db/db_iter.cc) over such a table.  Host only, no
+// GPU; the model-independent check of the device path and the baseline of
+// tools/bench_memtable.py and tools/bench_mt_range.py.
 #include "../../include/lvgpu/memtable.h"
 
 #include <algorithm>
@@ -100,6 +101,106 @@ int lv_memtable_get_host(const uint8_t *payload, size_t payload_bytes, const lv_
                 }
             }
         }
+    }
+    *result = r;
+    return 0;
+}
+
+// DBIter's forward walk (include/lvgpu/memtable.h, "Range"): the serial loop
+// of the header with `seen` as its state, the two seeks plain binary
+// searches.  Every entry is range-checked before its key is read.
+int lv_memtable_range_host(const uint8_t *payload, size_t payload_bytes, const lv_wb_op *ops, const uint32_t *order,
+                           const lv_mt_totals *totals, size_t op_cap, const uint8_t *qkeys, size_t qkeys_bytes,
+                           const lv_mt_range_query *query, uint32_t limit, uint64_t max_scan, uint32_t *hits,
+                           lv_mt_range_result *result) {
+    if (!totals || !query || !hits || !result || (!payload && payload_bytes) || (!qkeys && qkeys_bytes) || !limit ||
+        !max_scan)
+        return LV_ERR_INVALID;
+    const lv_mt_range_query &Q = *query;
+    const uint64_t n = totals->entries, s = Q.seq;
+    lv_mt_range_result r{0, 0, 0, 0, LV_MT_RANGE_DONE, 0, 0};
+    const bool resume = Q.flags & LV_MT_RANGE_RESUME, has_hi = Q.flags & LV_MT_RANGE_HAS_HI;
+    if (totals->status || n > op_cap || (n && (!ops || !order))) {
+        r.status = LV_MT_GET_NO_TABLE;
+    } else if (s > LV_MT_MAX_SEQUENCE) {
+        r.status = LV_MT_GET_BAD_SEQ;
+    } else if ((Q.flags & ~(LV_MT_RANGE_HAS_HI | LV_MT_RANGE_RESUME | LV_MT_RANGE_SEEN)) ||
+               ((Q.flags & LV_MT_RANGE_SEEN) && !resume) || (!resume && !extent_ok(Q.lo_off, Q.lo_len, qkeys_bytes)) ||
+               (has_hi && !extent_ok(Q.hi_off, Q.hi_len, qkeys_bytes)) || (resume && Q.pos > n)) {
+        r.status = LV_MT_GET_BAD_QUERY;
+    }
+    if (r.status) {
+        *result = r;
+        return 0;
+    }
+    bool table_ok = true;
+    // entry i's op, or null (and the table is not the build's) if it is out of range
+    auto entry = [&](uint64_t i) -> const lv_wb_op * {
+        const uint32_t idx = order[i];
+        if (idx >= op_cap || !extent_ok(ops[idx].key_off, ops[idx].key_len, payload_bytes)) {
+            table_ok = false;
+            return nullptr;
+        }
+        return &ops[idx];
+    };
+    // the first position whose entry is not less than (key, tag); with_tag false: whose user key is >= key
+    auto lower = [&](const uint8_t *key, size_t len, uint64_t tag, bool with_tag) -> uint64_t {
+        uint64_t lo = 0, hi = n;
+        while (lo < hi && table_ok) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            const lv_wb_op *o = entry(mid);
+            if (!o) break;
+            const int c = user_key_compare(payload + o->key_off, o->key_len, key, len);
+            if (c < 0 || (with_tag && c == 0 && o->tag > tag))
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        return lo;
+    };
+    uint64_t start = Q.pos, end = n;
+    if (!resume) start = lower(qkeys + Q.lo_off, Q.lo_len, (s << 8) | LV_WB_TYPE_VALUE, true);
+    if (has_hi && table_ok) end = lower(qkeys + Q.hi_off, Q.hi_len, 0, false);
+    bool seen = resume && (Q.flags & LV_MT_RANGE_SEEN);
+    uint64_t p = start, examined = 0, unparsed = 0;
+    uint32_t count = 0, status = LV_MT_RANGE_DONE;
+    const lv_wb_op *prev = nullptr;  // e_{p-1} once it has been checked
+    while (table_ok) {
+        if (count == limit) {
+            status = LV_MT_RANGE_MORE_LIMIT;
+            break;
+        }
+        if (p >= end) break;
+        if (examined == max_scan) {
+            status = LV_MT_RANGE_MORE_SCAN;
+            break;
+        }
+        if (p && !prev && !(prev = entry(p - 1))) break;
+        const lv_wb_op *e = entry(p);
+        if (!e) break;
+        ++p, ++examined;
+        if (!prev || user_key_compare(payload + prev->key_off, prev->key_len, payload + e->key_off, e->key_len) != 0)
+            seen = false;  // e starts a group
+        prev = e;
+        const uint64_t type = e->tag & 0xff;
+        if (type > LV_WB_TYPE_VALUE) {
+            ++unparsed;
+            continue;
+        }
+        if ((e->tag >> 8) > s || seen) continue;
+        seen = true;
+        if (type != LV_WB_TYPE_VALUE) continue;
+        hits[count++] = order[p - 1];
+    }
+    if (!table_ok) {
+        r.status = LV_MT_GET_NO_TABLE;
+    } else {
+        r.seek_pos = start;
+        r.next_pos = p;
+        r.unparsed = unparsed;
+        r.count = count;
+        r.status = status;
+        r.seen = seen;
     }
     *result = r;
     return 0;

@@ -14,6 +14,12 @@ lvgpu.write_batch in memtable order (internal-key order) and MemTable::get
     get_device(table, qkeys, q_off, q_len, q_seq)
                                       lv_memtable_get_device: a uint8 CUDA tensor of
                                       lv_mt_get_result (RESULT_DTYPE), asynchronous
+    pack_range_queries(queries)       (qkeys bytes, RANGE_QUERY_DTYPE array) of range queries
+    range_host(payload, ops, order, totals, qkeys, query, limit, max_scan)
+                                      lv_memtable_range_host: (hits, result dict)
+    range_device(table, queries, qkeys, limit, max_scan)
+                                      lv_memtable_range_device (DBIter's forward walk for a
+                                      batch of ranges): a Ranges of CUDA tensors, asynchronous
 """
 from __future__ import annotations
 
@@ -37,6 +43,14 @@ MT_PREFIX = 16
 RESULT_DTYPE = np.dtype([("val_off", "<u8"), ("val_len", "<u4"), ("op", "<u4"), ("status", "<u4"),
                          ("reserved", "<u4")])
 assert RESULT_DTYPE.itemsize == 24
+
+RANGE_HAS_HI, RANGE_RESUME, RANGE_SEEN = 1, 2, 4                      # LV_MT_RANGE_* query flags
+RANGE_DONE, RANGE_MORE_LIMIT, RANGE_MORE_SCAN = 0, 1, 2               # LV_MT_RANGE_* statuses; 3-5 are Get's
+RANGE_QUERY_DTYPE = np.dtype([("lo_off", "<u8"), ("hi_off", "<u8"), ("seq", "<u8"), ("pos", "<u8"),
+                              ("lo_len", "<u4"), ("hi_len", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+RANGE_RESULT_DTYPE = np.dtype([("seek_pos", "<u8"), ("next_pos", "<u8"), ("unparsed", "<u8"), ("count", "<u4"),
+                               ("status", "<u4"), ("seen", "<u4"), ("reserved", "<u4")])
+assert RANGE_QUERY_DTYPE.itemsize == 48 and RANGE_RESULT_DTYPE.itemsize == 40
 
 
 class Totals(ctypes.Structure):
@@ -72,6 +86,10 @@ def _bind():
     L.lv_memtable_build_device.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, u32, vp, sz, vp]
     L.lv_memtable_get_device.restype = ctypes.c_int
     L.lv_memtable_get_device.argtypes = [vp, sz, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, u32, vp]
+    L.lv_memtable_range_host.restype = ctypes.c_int
+    L.lv_memtable_range_host.argtypes = [vp, sz, vp, vp, ctypes.POINTER(Totals), sz, vp, sz, vp, u32, u64, vp, vp]
+    L.lv_memtable_range_device.restype = ctypes.c_int
+    L.lv_memtable_range_device.argtypes = [vp, sz, vp, vp, vp, sz, vp, sz, vp, sz, u32, u64, vp, vp, u32, vp]
     _bound = True
     return L
 
@@ -241,3 +259,137 @@ def results(res, nq):
     """The first nq results of get_device's tensor as a structured array
     (RESULT_DTYPE; synchronises)."""
     return res[: nq * 24].cpu().numpy().view(RESULT_DTYPE).copy()
+
+
+# ---- lv_memtable_range_*: DBIter's forward walk over a sorted table ------------
+def pack_range_queries(queries, gaps=None):
+    """(qkeys bytes, RANGE_QUERY_DTYPE array) of queries, each (lo, hi | None,
+    seq) -- a seek to lo at snapshot seq, up to hi if one is given -- or the
+    resume tuple ("resume", pos, seen, hi | None, seq), which continues a walk
+    from a result's (next_pos, seen).  gaps[i] bytes of 0xDD go in front of
+    query i's keys."""
+    qk, rows = bytearray(), np.zeros(len(queries), dtype=RANGE_QUERY_DTYPE)
+    for i, q in enumerate(queries):
+        if gaps is not None:
+            qk += b"\xDD" * int(gaps[i])
+        row = rows[i]
+        if q[0] == "resume":
+            _, pos, seen, hi, seq = q
+            row["pos"], row["flags"] = pos, RANGE_RESUME | (RANGE_SEEN if seen else 0)
+        else:
+            lo, hi, seq = q
+            row["lo_off"], row["lo_len"] = len(qk), len(lo)
+            qk += lo
+        if hi is not None:
+            row["hi_off"], row["hi_len"] = len(qk), len(hi)
+            row["flags"] |= RANGE_HAS_HI
+            qk += hi
+        row["seq"] = seq
+    return bytes(qk), rows
+
+
+def range_host(payload, ops, order, totals, qkeys, query, limit, max_scan, *, op_cap=None, canary=None):
+    """lv_memtable_range_host for one query (a RANGE_QUERY_DTYPE row over
+    `qkeys`): (hits[0, count) as a uint32 array, the result's fields as a
+    dict).  canary: a uint32 the hit slot holds first; the whole slot is then
+    returned, for checks of what was left untouched."""
+    L = _bind()
+    pb, pn = _buf(payload)
+    kb, kn = _buf(qkeys)
+    arr, ap = _ops_array(ops)
+    order = np.ascontiguousarray(order, dtype=np.uint32)
+    tot = Totals(totals["entries"], totals["user_keys"], totals["status"])
+    row = np.ascontiguousarray(np.asarray(query, dtype=RANGE_QUERY_DTYPE).reshape(1))
+    hits = np.full(max(int(limit), 1), 0 if canary is None else canary, dtype=np.uint32)
+    res = np.zeros(1, dtype=RANGE_RESULT_DTYPE)
+    rc = L.lv_memtable_range_host(pb, pn, ap, order.ctypes.data if order.size else None, ctypes.byref(tot),
+                                  arr.size if op_cap is None else op_cap, kb, kn, row.ctypes.data, limit, max_scan,
+                                  hits.ctypes.data, res.ctypes.data)
+    if rc != 0:
+        raise LvError(f"lv_memtable_range_host: {rc}")
+    r = {k: int(res[0][k]) for k in RANGE_RESULT_DTYPE.names}
+    return (hits if canary is not None else hits[: r["count"]].copy()), r
+
+
+class Ranges:
+    """Outputs of range_device, CUDA tensors written asynchronously: hits_t
+    (int32, nq slots of `limit` op indices and the guard) and results_t (uint8,
+    nq lv_mt_range_result and the guard)."""
+
+    def __init__(self, nq, limit, hits_t, results_t, keep):
+        self.nq, self.limit, self.hits_t, self.results_t = nq, limit, hits_t, results_t
+        self._keep = keep  # the queries and their keys, until the work has run
+
+    def sync(self):
+        """Waits for the call: (hits as a uint32 array of shape (nq, limit),
+        results as a RANGE_RESULT_DTYPE array).  Row q's hits are its first
+        results[q]["count"] entries."""
+        import torch
+        torch.cuda.synchronize(self.results_t.device)
+        self._keep = None
+        res = self.results_t[: self.nq * 40].cpu().numpy().view(RANGE_RESULT_DTYPE).copy()
+        hits = self.hits_t[: self.nq * self.limit].cpu().numpy().view(np.uint32).reshape(self.nq, self.limit).copy()
+        return hits, res
+
+    def hit_lists(self):
+        """sync(), each query's hits cut to its count: (list of lists, results)."""
+        hits, res = self.sync()
+        return [hits[q, : int(res[q]["count"])].tolist() for q in range(self.nq)], res
+
+
+def range_device(table, queries, qkeys, limit, max_scan, *, nq=None, stream=None, fill=None, guard: int = 0,
+                 flags: int = 0):
+    """lv_memtable_range_device over a Table (a build's, a Scanned.memtable()
+    or a lvgpu.compact.Filtered): its payload, ops, order and totals, read on
+    the device.  `queries` is a RANGE_QUERY_DTYPE array (copied to the device
+    here) or a uint8 CUDA tensor of 48-byte lv_mt_range_query rows that is
+    already there, `qkeys` the bytes their extents point into (bytes, or a
+    uint8 CUDA tensor).  fill, a byte value, initialises d_hits and d_results
+    with it first and guard allocates that many more bytes behind each
+    (canaries).  Returns a Ranges; asynchronous on `stream`."""
+    import torch
+    from . import _dev_ptr, _stream_ptr
+    L = _bind()
+    dev = table.payload.device
+    if torch.is_tensor(queries):
+        if queries.dtype != torch.uint8 or queries.device != dev:
+            raise LvError("queries must be a uint8 tensor on the payload's device")
+        d_q = queries
+        nq = queries.numel() // 48 if nq is None else int(nq)
+        if queries.numel() < nq * 48:
+            raise LvError("queries must hold nq rows of 48 bytes")
+    else:
+        rows = np.ascontiguousarray(queries, dtype=RANGE_QUERY_DTYPE)
+        nq = rows.size if nq is None else int(nq)
+        if rows.size < nq:
+            raise LvError("queries must hold nq rows")
+        d_q = torch.frombuffer(bytearray(rows.tobytes()) + bytearray(8), dtype=torch.uint8).to(dev)
+    if torch.is_tensor(qkeys):
+        if qkeys.dtype != torch.uint8 or qkeys.device != dev:
+            raise LvError("qkeys must be a uint8 tensor on the payload's device")
+        d_qk, qk_bytes = qkeys, qkeys.numel()
+    else:
+        qk_bytes = len(qkeys)
+        d_qk = torch.frombuffer(bytearray(qkeys), dtype=torch.uint8).to(dev) if qk_bytes else None
+    limit, max_scan = int(limit), int(max_scan)
+
+    def alloc(used):
+        nbytes = (max(used, 16) + guard + 7) & ~7
+        if fill is None:
+            return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return torch.full((nbytes,), fill, dtype=torch.uint8, device=dev)
+
+    hits_t = alloc(nq * max(limit, 1) * 4).view(torch.int32)
+    results_t = alloc(nq * 40)
+    op_cap = int(table.op_cap)
+    with torch.cuda.device(dev):  # the C call runs on the current device
+        rc = L.lv_memtable_range_device(_dev_ptr(table.payload, "payload") if table.payload.numel() else None,
+                                        table.payload.numel(), _dev_ptr(table.ops_t, "ops") if op_cap else None,
+                                        _dev_ptr(table.order_t, "order") if op_cap else None,
+                                        _dev_ptr(table.totals, "totals"), op_cap,
+                                        _dev_ptr(d_qk, "qkeys") if qk_bytes else None, qk_bytes,
+                                        _dev_ptr(d_q, "queries"), nq, limit, max_scan, _dev_ptr(hits_t, "hits"),
+                                        _dev_ptr(results_t, "results"), flags, _stream_ptr(stream))
+    if rc != 0:
+        raise LvError(f"lv_memtable_range_device: {lib().lv_last_error().decode()}")
+    return Ranges(nq, limit, hits_t, results_t, (table, d_q, d_qk))
