@@ -25,9 +25,11 @@
  * Out of scope: the memtable / immutable-memtable fall-through in front
  * (DBImpl::Get's first two steps: lv_memtable_get_device has the same query
  * arrays and status numbers); UpdateStats / allowed_seeks bookkeeping
- * (seek_file and files_read are what it needs); VersionEdit encode / decode;
+ * (seek_file and files_read are what it needs);
  * the table cache; iterators and range reads over a version; compression.
- * (A compaction's output as a run of tables with their records:
+ * (VersionEdit encode / decode, the record of the MANIFEST:
+ * lv_version_edit_decode_device / lv_version_edit_encode_device,
+ * version_edit.h.  A compaction's output as a run of tables with their records:
  * lv_compact_output_device, compact.h.  Range reads: lv_memtable_range_device,
  * memtable.h, is DBIter's forward walk over a sorted memtable quadruple; for
  * now a version's range goes through lv_sst_scan_device per table, appended,

@@ -11,6 +11,7 @@
 #include <time.h>
 
 #include "../include/lvgpu/wal.h"
+#include "../include/lvgpu/version_edit.h"
 #include "../include/lvgpu/write_batch.h"
 
 static double now_s(void) {
@@ -94,6 +95,48 @@ double lv_replay_write_batch(const uint8_t *payload, const uint64_t *off, const 
         const double el = now_s() - t0;
         if (best < 0 || el < best) best = el;
         *total = at;
+        *bad = nbad;
+    }
+    return best;
+}
+
+/* tools/bench_version_edit.py's host route: lv_version_edit_decode_host over
+ * every record payload[off[r], off[r] + len[r]) on one core, the edits and the
+ * rows written end to end as lv_version_edit_decode_device lays them out
+ * (offsets into the payload); best of `reps` passes in seconds, counts[0..3) =
+ * the file, deleted and pointer rows of one pass, *bad = its records with a
+ * status other than LV_VE_OK (-1.0 if a capacity is too small). */
+double lv_replay_version_edit(const uint8_t *payload, const uint64_t *off, const uint64_t *len, size_t n,
+                              lv_ve_edit *edits, lv_ve_file *files, size_t file_cap, lv_ve_deleted *deleted,
+                              size_t deleted_cap, lv_ve_pointer *pointers, size_t pointer_cap, int reps,
+                              uint64_t *counts, uint64_t *bad) {
+    double best = -1.0;
+    for (int r = 0; r < reps; ++r) {
+        const double t0 = now_s();
+        size_t nf = 0, nd = 0, np = 0;
+        uint64_t nbad = 0;
+        for (size_t i = 0; i < n; ++i) {
+            size_t c[3];
+            const uint32_t st = lv_version_edit_decode_host(payload + off[i], (size_t)len[i], edits + i, files + nf,
+                                                            file_cap - nf, deleted + nd, deleted_cap - nd, pointers + np,
+                                                            pointer_cap - np, c);
+            if (c[0] > file_cap - nf || c[1] > deleted_cap - nd || c[2] > pointer_cap - np) return -1.0;
+            if (edits[i].has & LV_VE_HAS_COMPARATOR) edits[i].comparator_off += off[i];
+            for (size_t k = 0; k < c[0]; ++k) {
+                files[nf + k].smallest_off += off[i];
+                files[nf + k].largest_off += off[i];
+            }
+            for (size_t k = 0; k < c[2]; ++k) pointers[np + k].key_off += off[i];
+            nf += c[0];
+            nd += c[1];
+            np += c[2];
+            nbad += st != LV_VE_OK;
+        }
+        const double el = now_s() - t0;
+        if (best < 0 || el < best) best = el;
+        counts[0] = nf;
+        counts[1] = nd;
+        counts[2] = np;
         *bad = nbad;
     }
     return best;
