@@ -379,12 +379,12 @@ __global__ __launch_bounds__(kSbThreads) void co_file_tail(const SbArgs A, const
             e[0] = LV_SST_NO_COMPRESSION;
             // the metaindex block's one entry: shared 0, the name, the filter block's handle
             constexpr char name[] = LV_SST_BLOOM_NAME;
-            m = sb_put_varint(m, 0);
-            m = sb_put_varint(m, kSbBloomName);
-            m = sb_put_varint(m, L.meta_size - 3 - kSbBloomName - 8);
+            m = put_varint(m, 0);
+            m = put_varint(m, kSbBloomName);
+            m = put_varint(m, L.meta_size - 3 - kSbBloomName - 8);
             for (uint32_t t = 0; t < kSbBloomName; ++t) *m++ = static_cast<uint8_t>(name[t]);
-            m = sb_put_varint(m, L.filter_off);
-            m = sb_put_varint(m, L.filter_size);
+            m = put_varint(m, L.filter_off);
+            m = put_varint(m, L.filter_size);
             *h++ = L.filter_off;
             *h++ = L.filter_size;
             A.idx_off[per * k + 1] = L.file_off + L.filter_off;
@@ -398,10 +398,10 @@ __global__ __launch_bounds__(kSbThreads) void co_file_tail(const SbArgs A, const
         *h++ = L.index_size;
         sb_put_fixed32(file + L.index_off + c.idx_bytes + 4 * blocks, static_cast<uint32_t>(blocks));
         uint8_t *f = file + L.index_off + L.index_size + LV_SST_TRAILER_SIZE, *q = f;
-        q = sb_put_varint(q, L.meta_off);
-        q = sb_put_varint(q, L.meta_size);
-        q = sb_put_varint(q, L.index_off);
-        q = sb_put_varint(q, L.index_size);
+        q = put_varint(q, L.meta_off);
+        q = put_varint(q, L.meta_size);
+        q = put_varint(q, L.index_off);
+        q = put_varint(q, L.index_size);
         while (q < f + 40) *q++ = 0;
         for (uint32_t t = 0; t < 8; ++t) *q++ = static_cast<uint8_t>(LV_SST_MAGIC >> (8 * t));
         // the records: what the opens and lv_version_file_device find in the image

@@ -91,24 +91,6 @@ constexpr uint32_t kSpanBytes = 4096;
 constexpr uint64_t kWgsPerCu = LVK_HASH_WGS_PER_CU;
 constexpr uint32_t kSpanPad = 20;  // dwords past the span a masked fast-path read may address
 
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const uint64_t o = __shfl_xor(v, m);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const uint64_t o = __shfl_xor(v, m);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 // hash.rs:25-48 of one key of any length read straight from memory
 // (dword-aligned reads, funnel-shifted by the key's misalignment, never a
 // dword past its last byte); h arrives as seed ^ (kM * L).

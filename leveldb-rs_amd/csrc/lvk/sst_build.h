@@ -129,24 +129,6 @@ __device__ __forceinline__ uint64_t sb_entries(const SbArgs &A) {
     return (A.mt->status || n > A.op_cap) ? 0 : n;
 }
 
-__device__ __forceinline__ uint32_t sb_varint_len(uint64_t v) {
-    uint32_t n = 1;
-    while (v >= 128) {
-        v >>= 7;
-        ++n;
-    }
-    return n;
-}
-
-__device__ __forceinline__ uint8_t *sb_put_varint(uint8_t *p, uint64_t v) {
-    while (v >= 128) {
-        *p++ = static_cast<uint8_t>(v | 0x80);
-        v >>= 7;
-    }
-    *p++ = static_cast<uint8_t>(v);
-    return p;
-}
-
 __device__ __forceinline__ void sb_put_fixed32(uint8_t *p, uint32_t v) {
     p[0] = static_cast<uint8_t>(v);
     p[1] = static_cast<uint8_t>(v >> 8);
@@ -221,8 +203,8 @@ __device__ __forceinline__ SbIndexEntry sb_index_entry(const SbArgs &A, uint64_t
     SbIndexEntry x;
     x.sep = sb_separator(A, e, last, o);
     x.klen = x.sep.copy + (x.sep.bump ? 1 : 0) + 8;
-    x.hlen = sb_varint_len(off) + sb_varint_len(raw);
-    x.size = 1 + sb_varint_len(x.klen) + sb_varint_len(x.hlen) + x.klen + x.hlen;
+    x.hlen = varint_len(off) + varint_len(raw);
+    x.size = 1 + varint_len(x.klen) + varint_len(x.hlen) + x.klen + x.hlen;
     return x;
 }
 
@@ -263,7 +245,7 @@ __device__ __forceinline__ CoLayout co_sizes(uint32_t bpk, uint64_t data_bytes, 
         L.filter_off = data_bytes;
         L.filter_size = filt_bytes + 4 * filters + 5;
         L.meta_off = L.filter_off + L.filter_size + LV_SST_TRAILER_SIZE;
-        L.meta_size = 3 + kSbBloomName + sb_varint_len(L.filter_off) + sb_varint_len(L.filter_size) + 8;
+        L.meta_size = 3 + kSbBloomName + varint_len(L.filter_off) + varint_len(L.filter_size) + 8;
     }
     L.index_off = L.meta_off + L.meta_size + LV_SST_TRAILER_SIZE;
     L.index_size = idx_bytes + 4 * blocks + 4;
@@ -354,9 +336,9 @@ __device__ __forceinline__ void sb_emit_entry(const SbArgs &A, uint64_t i, bool 
         const uint64_t rel = i > s ? sb_buffer(A, s, i - 1, &r) : 0;
         const uint64_t ulen = o.key_len, klen = ulen + 8, sh = restart ? 0 : A.shared[i];
         uint8_t *p = A.file + B.at + rel;
-        p = sb_put_varint(p, sh);
-        p = sb_put_varint(p, klen - sh);
-        p = sb_put_varint(p, o.val_len);
+        p = put_varint(p, sh);
+        p = put_varint(p, klen - sh);
+        p = put_varint(p, o.val_len);
         if (sh < ulen) {
             kd = p;
             ks = A.payload + o.key_off + sh;
@@ -381,9 +363,9 @@ __device__ __forceinline__ void sb_emit_entry(const SbArgs &A, uint64_t i, bool 
             const uint64_t at = X.end - x.size;
             sb_put_fixed32(X.ix + X.idx_bytes + 4 * X.b, static_cast<uint32_t>(at));
             uint8_t *q = X.ix + at;
-            q = sb_put_varint(q, 0);
-            q = sb_put_varint(q, x.klen);
-            q = sb_put_varint(q, x.hlen);
+            q = put_varint(q, 0);
+            q = put_varint(q, x.klen);
+            q = put_varint(q, x.hlen);
             xd = q;
             xs = A.payload + le.key_off;
             xn = x.sep.copy;
@@ -394,8 +376,8 @@ __device__ __forceinline__ void sb_emit_entry(const SbArgs &A, uint64_t i, bool 
                 tg = (LV_MT_MAX_SEQUENCE << 8) | 1u;  // MAXTAG
             }
             for (uint32_t t = 0; t < 8; ++t) *q++ = static_cast<uint8_t>(tg >> (8 * t));
-            q = sb_put_varint(q, B.off);
-            q = sb_put_varint(q, raw);
+            q = put_varint(q, B.off);
+            q = put_varint(q, raw);
         }
     }
     group_copy<kSbCopyLanes, kSbWaveCopy>(kd, ks, kn, lane);

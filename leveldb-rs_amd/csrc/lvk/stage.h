@@ -8,10 +8,13 @@
 // The stages hand each other an op table (32-byte lv_wb_op entries over a
 // payload or an arena) and are built from the same few parts: an extent check
 // on what an op points at, the op as two 16-B accesses, user keys compared as
-// bytes, a two-level scan (tile-local in LDS, then one wave over the tiles'
-// sums) and a copy of long byte strings that the lanes of a wave share.  Each part is here once; the
+// bytes, a u64 shuffle and the wave's sum, least and greatest, a varint's
+// length and store, the record of a row by its bounds, a two-level scan
+// (tile-local in LDS, then one wave over the tiles' sums) and a copy of long
+// byte strings that the lanes of a wave share.  Each part is here once; the
 // tile sizes, thread counts and copy knobs stay with the stage that owns them
-// and come in as template arguments.
+// and come in as template arguments.  What only the two record decoders share
+// (byte sources, varint reads, the wave's dispatch) is lvk/records.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -96,6 +99,66 @@ __device__ __forceinline__ uint64_t wave_incl(uint64_t v, uint32_t lane) {
         if (lane >= o) v += u;
     }
     return v;
+}
+
+// Lane src's v, and v summed / its least / its greatest over the 64 lanes of a
+// wave, in every lane.  Every lane of the wave calls them, as above.
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, uint32_t src) {
+    return __shfl(static_cast<unsigned long long>(v), static_cast<int>(src), 64);
+}
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) v += __shfl_xor(static_cast<unsigned long long>(v), static_cast<int>(d), 64);
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_min(uint64_t v) {
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) {
+        const uint64_t o = __shfl_xor(static_cast<unsigned long long>(v), static_cast<int>(d), 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_max(uint64_t v) {
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) {
+        const uint64_t o = __shfl_xor(static_cast<unsigned long long>(v), static_cast<int>(d), 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// A varint's length, and its bytes stored at p: returns the byte behind them.
+__device__ __forceinline__ uint32_t varint_len(uint64_t v) {
+    uint32_t n = 1;
+    while (v >= 128) {
+        v >>= 7;
+        ++n;
+    }
+    return n;
+}
+__device__ __forceinline__ uint8_t *put_varint(uint8_t *p, uint64_t v) {
+    while (v >= 128) {
+        *p++ = static_cast<uint8_t>(v | 0x80);
+        v >>= 7;
+    }
+    *p++ = static_cast<uint8_t>(v);
+    return p;
+}
+
+// The record of row i of an ascending bounds array: the r with
+// bounds[r] <= i < bounds[r + 1], searched in [lo, hi] (it lies there).
+// Empty records make equal bounds: the last of them whose bound is <= i is
+// the one.  Bounded by the 32 bits of a record index.
+__device__ __forceinline__ uint64_t record_of(const uint64_t *bounds, uint64_t i, uint64_t lo, uint64_t hi) {
+    for (uint32_t it = 0; it < 33 && lo < hi; ++it) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;  // in (lo, hi]
+        if (bounds[mid] <= i)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
 }
 
 // In-place inclusive scan of the LDS array s[0, kTile) with stride st: the

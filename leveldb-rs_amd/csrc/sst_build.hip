@@ -164,8 +164,8 @@ __global__ __launch_bounds__(kSbThreads) void sb_sizes(const SbArgs A) {
                 } else {
                     if (i) sh = sb_shared(A, p, o);
                     const uint64_t klen = static_cast<uint64_t>(o.key_len) + 8, vlen = o.val_len;
-                    nr = sb_varint_len(sh) + sb_varint_len(klen - sh) + sb_varint_len(vlen) + (klen - sh) + vlen;
-                    d = 1 + sb_varint_len(klen) + sb_varint_len(vlen) + klen + vlen - nr;
+                    nr = varint_len(sh) + varint_len(klen - sh) + varint_len(vlen) + (klen - sh) + vlen;
+                    d = 1 + varint_len(klen) + varint_len(vlen) + klen + vlen - nr;
                 }
             }
             A.shared[i] = sh;
@@ -382,7 +382,7 @@ __global__ void sb_plan(const SbArgs A) {
             bt.filter_keys = n;
             if (bt.filter_size >= kSbLarge) t.status |= LV_SST_BUILD_BLOCK_LARGE;
             t.metaindex_offset = bt.filter_offset + bt.filter_size + LV_SST_TRAILER_SIZE;
-            t.metaindex_size = 3 + kSbBloomName + sb_varint_len(bt.filter_offset) + sb_varint_len(bt.filter_size) + 8;
+            t.metaindex_size = 3 + kSbBloomName + varint_len(bt.filter_offset) + varint_len(bt.filter_size) + 8;
         }
         t.index_offset = t.metaindex_offset + t.metaindex_size + LV_SST_TRAILER_SIZE;
         t.index_size = h->idx_bytes + 4 * nb + 4;
@@ -484,21 +484,21 @@ __global__ __launch_bounds__(kSbThreads) void sb_tail(const SbArgs A) {
             // the metaindex block's one entry: shared 0, the name, the filter block's handle
             constexpr char name[] = LV_SST_BLOOM_NAME;
             meta_size = bh->meta_size;
-            m = sb_put_varint(m, 0);
-            m = sb_put_varint(m, kSbBloomName);
-            m = sb_put_varint(m, meta_size - 3 - kSbBloomName - 8);
+            m = put_varint(m, 0);
+            m = put_varint(m, kSbBloomName);
+            m = put_varint(m, meta_size - 3 - kSbBloomName - 8);
             for (uint32_t t = 0; t < kSbBloomName; ++t) *m++ = static_cast<uint8_t>(name[t]);
-            m = sb_put_varint(m, bh->filter_off);
-            m = sb_put_varint(m, bh->filter_size);
+            m = put_varint(m, bh->filter_off);
+            m = put_varint(m, bh->filter_size);
         }
         sb_put_fixed32(m, 0);  // (an empty BlockBuilder: 00 00 00 00 01 00 00 00)
         sb_put_fixed32(m + 4, 1);
         sb_put_fixed32(A.file + h->index_off + h->idx_bytes + 4 * h->nblocks, static_cast<uint32_t>(h->nblocks));
         uint8_t *f = A.file + h->index_off + h->index_size + LV_SST_TRAILER_SIZE, *q = f;
-        q = sb_put_varint(q, h->meta_off);
-        q = sb_put_varint(q, meta_size);
-        q = sb_put_varint(q, h->index_off);
-        q = sb_put_varint(q, h->index_size);
+        q = put_varint(q, h->meta_off);
+        q = put_varint(q, meta_size);
+        q = put_varint(q, h->index_off);
+        q = put_varint(q, h->index_size);
         while (q < f + 40) *q++ = 0;
         for (uint32_t t = 0; t < 8; ++t) *q++ = static_cast<uint8_t>(LV_SST_MAGIC >> (8 * t));
     }

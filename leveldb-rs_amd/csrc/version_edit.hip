@@ -19,10 +19,12 @@
 //              records with rows are walked again.
 //
 // Count and emit share one walk (vd_walk), templated on the byte source and
-// the row sink.  The byte sources restate write_batch.hip's: a record of up
-// to kVdSmall bytes is walked by one lane over the aligned 16-byte granule
-// under the byte it needs; a longer one by its wave through an LDS window,
-// wave-uniformly, and lane k % 64 stores row k.
+// the row sink.  The byte sources, the varint reads, a record's class and the
+// wave's dispatch are the ones write_batch.hip uses, lvk/records.h's: a
+// record of up to kVdSmall bytes is walked by one lane over the aligned
+// 16-byte granule under the byte it needs (LaneSrc); a longer one by its wave
+// through an LDS window (WaveSrc), wave-uniformly, and lane k % 64 stores
+// row k.
 //
 // Encode is write_batch_encode.hip's shape, all or nothing: validate the
 // bounds; size every item (a record's scalar group or one row) with a tile
@@ -34,7 +36,9 @@
 //
 // Every grid is sized by the capacities, one workgroup per tile, no
 // grid-stride loop; the only loops whose trip count grows with the input are
-// the carries' rounds of 64 tiles.  All positions are u64.
+// the carries' rounds of 64 tiles.  All positions are u64.  The wave
+// reductions, the varint's length and store and the record of a row
+// (record_of) are lvk/stage.h's.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -43,7 +47,7 @@
 #include "../../include/lvgpu/version_edit.h"
 #include "lv_internal.h"
 #include "lvh.h"
-#include "lvk/stage.h"
+#include "lvk/records.h"
 
 namespace lvk {
 
@@ -54,8 +58,6 @@ constexpr uint32_t kVdWaves = kVdThreads / 64;
 constexpr uint32_t kVdSmall = 16384;                  // records up to this many bytes: one lane each
 constexpr uint32_t kVdWindow = 4096;                  // LDS window of a wave-class record, bytes
 constexpr uint32_t kVdRound = 64 * 16;                // one load of the wave: 64 lanes x 16 B
-constexpr uint32_t kVdWinPad = 16;                    // LDS behind a window: the 12-byte register refill may run into it
-static_assert(kVdWindow % kVdRound == 0 && kVdWindow > kVdRound, "a window is whole rounds, more than one");
 
 struct VdHead {  // workspace, zeroed by vd_init
     unsigned long long bad;
@@ -74,91 +76,6 @@ struct VdArgs {
     uint64_t *cnt;      // [3 rec_cap] file, deleted and pointer rows of each record
     uint64_t *tsum;     // [3 tiles] the tiles' rows, then (vd_tiles) the rows before the tile
     uint64_t *tinfo;    // [6 tiles] the tile's first bad record (~0: none), 1 + the last record before it with each has bit
-};
-
-__device__ __forceinline__ uint64_t vd_records(const VdArgs &A) {
-    if (A.upstream && *A.upstream) return 0;
-    const uint64_t n = *A.records;
-    return n > A.rec_cap ? 0ull : n;
-}
-
-// ---- byte sources (write_batch.hip's, restated) ------------------------------
-// One lane: the aligned granule under the last byte asked for, in registers.
-struct VdLaneSrc {
-    const uint8_t *p;
-    uint64_t gi;
-    u32x4 g;
-    __device__ __forceinline__ explicit VdLaneSrc(const uint8_t *payload) : p(payload), gi(~0ull), g{0, 0, 0, 0} {}
-    __device__ __forceinline__ uint32_t byte(uint64_t a) {
-        const uint64_t addr = reinterpret_cast<uint64_t>(p) + a;
-        const uint64_t q = addr >> 4;
-        if (q != gi) {
-            g = *reinterpret_cast<const u32x4 *>(q << 4);
-            gi = q;
-        }
-        const uint32_t i = static_cast<uint32_t>(addr) & 15u;
-        const uint32_t w = i < 8 ? (i < 4 ? g.x : g.y) : (i < 12 ? g.z : g.w);
-        return (w >> (8 * (i & 3u))) & 0xffu;
-    }
-};
-
-// One wave: a window of kVdWindow bytes in LDS from an aligned address.  A
-// window opens where the parser lands after a skip, with its first round;
-// when the walk runs on past that round, the rest of the window is loaded.
-// Only granules that begin before the record's end are loaded (the rest read
-// as 0 and are never asked for).  Every call is wave-uniform.
-struct VdWaveSrc {
-    const uint8_t *p;
-    uint8_t *lds;
-    uint64_t lo, end;  // window start address (16-B aligned; ~0: none), record end address
-    uint32_t have;     // bytes of the window that are loaded
-    uint32_t lane;
-    uint64_t ra, rw;   // the rn (<= 8) bytes from address ra on, in a register pair
-    uint32_t rn;
-    __device__ __forceinline__ VdWaveSrc(const uint8_t *payload, uint8_t *window, uint64_t rec_end, uint32_t l)
-        : p(payload), lds(window), lo(~0ull), end(reinterpret_cast<uint64_t>(payload) + rec_end), have(0), lane(l),
-          ra(0), rw(0), rn(0) {}
-    __device__ __forceinline__ void load(uint32_t from, uint32_t to) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // the reads of the old window are done
-        for (uint32_t slot = from / 16 + lane; slot < to / 16; slot += 64) {
-            const uint64_t ga = lo + static_cast<uint64_t>(slot) * 16;
-            u32x4 v{0, 0, 0, 0};
-            if (ga < end) v = *reinterpret_cast<const u32x4 *>(ga);
-            reinterpret_cast<u32x4 *>(lds)[slot] = v;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    __device__ __forceinline__ void refill(uint64_t addr) {
-        if (lo == ~0ull || addr < lo || addr - lo >= kVdWindow) {
-            lo = addr & ~15ull;
-            have = 0;
-        }
-        const uint32_t at = static_cast<uint32_t>(addr - lo);
-        if (at >= have) {  // a new window: its first round; running on: the rest
-            const uint32_t to = have ? kVdWindow : kVdRound;
-            load(have, to);
-            have = to;
-        }
-        // 8 bytes from `at`: three aligned words and a byte shift (the last
-        // may lie in the pad behind the window; only rn bytes are ever used)
-        const uint32_t *w = reinterpret_cast<const uint32_t *>(lds + (at & ~3u));
-        const uint32_t d0 = w[0], d1 = w[1], d2 = w[2], s = at & 3u;
-        const uint32_t l32 = __builtin_amdgcn_alignbyte(d1, d0, s), h32 = __builtin_amdgcn_alignbyte(d2, d1, s);
-        rw = (static_cast<uint64_t>(h32) << 32) | l32;
-        ra = addr;
-        rn = have - at < 8u ? have - at : 8u;
-    }
-    __device__ __forceinline__ uint32_t byte(uint64_t a) {
-        const uint64_t addr = reinterpret_cast<uint64_t>(p) + a;
-        uint64_t d = addr - ra;
-        if (d >= rn) {
-            refill(addr);
-            d = 0;
-        }
-        return static_cast<uint32_t>(rw >> (8u * static_cast<uint32_t>(d))) & 0xffu;
-    }
 };
 
 // ---- row sinks -----------------------------------------------------------------
@@ -193,48 +110,12 @@ struct VdRes {
     uint64_t nf, nd, np;
 };
 
-// coding.rs:186-204 over the record's remaining input [*pos, n).
-template <class Src>
-__device__ __forceinline__ bool vd_varint32(Src &src, uint64_t off, uint64_t n, uint64_t *pos, uint32_t *v) {
-    uint32_t result = 0;
-    uint64_t p = *pos;
-    for (uint32_t shift = 0; shift <= 28 && p < n; shift += 7) {
-        const uint32_t b = src.byte(off + p);
-        ++p;
-        result |= (b & 0x7fu) << shift;  // bits above 31 of the fifth byte fall off
-        if (!(b & 0x80u)) {
-            *pos = p;
-            *v = result;
-            return true;
-        }
-    }
-    return false;
-}
-
-// coding.rs:223-241.
-template <class Src>
-__device__ __forceinline__ bool vd_varint64(Src &src, uint64_t off, uint64_t n, uint64_t *pos, uint64_t *v) {
-    uint64_t result = 0;
-    uint64_t p = *pos;
-    for (uint32_t shift = 0; shift <= 63 && p < n; shift += 7) {
-        const uint64_t b = src.byte(off + p);
-        ++p;
-        result |= (b & 0x7fu) << shift;  // bits above 63 of the tenth byte fall off
-        if (!(b & 0x80u)) {
-            *pos = p;
-            *v = result;
-            return true;
-        }
-    }
-    return false;
-}
-
 // coding.rs:294-305; the body is skipped, not read.  *at = its offset in the payload.
 template <class Src>
 __device__ __forceinline__ uint32_t vd_varstring(Src &src, uint64_t off, uint64_t n, uint64_t *pos, uint64_t *at,
                                                  uint32_t *len) {
     uint32_t l;
-    if (!vd_varint32(src, off, n, pos, &l)) return LV_VE_BAD_VARINT32;
+    if (!varint32(src, off, n, pos, &l)) return LV_VE_BAD_VARINT32;
     if (n - *pos < l) return LV_VE_BAD_LENGTH;
     *at = off + *pos;
     *len = l;
@@ -246,7 +127,7 @@ __device__ __forceinline__ uint32_t vd_varstring(Src &src, uint64_t off, uint64_
 template <class Src>
 __device__ __forceinline__ uint32_t vd_level(Src &src, uint64_t off, uint64_t n, uint64_t *pos, uint32_t *level,
                                              uint32_t *flags) {
-    if (!vd_varint32(src, off, n, pos, level)) return LV_VE_BAD_VARINT32;
+    if (!varint32(src, off, n, pos, level)) return LV_VE_BAD_VARINT32;
     if (*level & 0x80000000u)
         *flags |= LV_VE_FLAG_NEG_LEVEL;
     else if (*level >= LV_VE_NUM_LEVELS)
@@ -264,7 +145,7 @@ __device__ __forceinline__ VdRes vd_walk(Src &src, Sink &sink, uint64_t off, uin
     uint32_t st = LV_VE_OK;
     while (st == LV_VE_OK) {
         uint32_t tag;
-        if (!vd_varint32(src, off, n, &pos, &tag)) {
+        if (!varint32(src, off, n, &pos, &tag)) {
             if (pos < n) st = LV_VE_INVALID_TAG;
             break;
         }
@@ -274,7 +155,7 @@ __device__ __forceinline__ VdRes vd_walk(Src &src, Sink &sink, uint64_t off, uin
                 e.has |= LV_VE_HAS_COMPARATOR;
         } else if (tag == 2 || tag == 3 || tag == 4 || tag == 9) {
             uint64_t v;
-            if (!vd_varint64(src, off, n, &pos, &v)) {
+            if (!varint64(src, off, n, &pos, &v)) {
                 st = LV_VE_BAD_VARINT64;
             } else if (tag == 2) {
                 e.log_number = v;
@@ -299,7 +180,7 @@ __device__ __forceinline__ VdRes vd_walk(Src &src, Sink &sink, uint64_t off, uin
         } else if (tag == 6) {
             lv_ve_deleted d{};
             if ((st = vd_level(src, off, n, &pos, &d.level, &e.flags)) != LV_VE_OK) break;
-            if (!vd_varint64(src, off, n, &pos, &d.number)) {
+            if (!varint64(src, off, n, &pos, &d.number)) {
                 st = LV_VE_BAD_VARINT64;
                 break;
             }
@@ -308,7 +189,7 @@ __device__ __forceinline__ VdRes vd_walk(Src &src, Sink &sink, uint64_t off, uin
         } else if (tag == 7) {
             lv_ve_file f{};
             if ((st = vd_level(src, off, n, &pos, &f.level, &e.flags)) != LV_VE_OK) break;
-            if (!vd_varint64(src, off, n, &pos, &f.number) || !vd_varint64(src, off, n, &pos, &f.file_size)) {
+            if (!varint64(src, off, n, &pos, &f.number) || !varint64(src, off, n, &pos, &f.file_size)) {
                 st = LV_VE_BAD_VARINT64;
                 break;
             }
@@ -326,50 +207,6 @@ __device__ __forceinline__ VdRes vd_walk(Src &src, Sink &sink, uint64_t off, uin
     return r;
 }
 
-__device__ __forceinline__ uint64_t vd_shfl64(uint64_t v, uint32_t src) {
-    return __shfl(static_cast<unsigned long long>(v), static_cast<int>(src), 64);
-}
-
-__device__ __forceinline__ uint64_t vd_wave_sum(uint64_t v) {
-#pragma unroll
-    for (uint32_t d = 32; d; d >>= 1) v += __shfl_xor(static_cast<unsigned long long>(v), static_cast<int>(d), 64);
-    return v;
-}
-__device__ __forceinline__ uint64_t vd_wave_min(uint64_t v) {
-#pragma unroll
-    for (uint32_t d = 32; d; d >>= 1) {
-        const uint64_t o = __shfl_xor(static_cast<unsigned long long>(v), static_cast<int>(d), 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t vd_wave_max(uint64_t v) {
-#pragma unroll
-    for (uint32_t d = 32; d; d >>= 1) {
-        const uint64_t o = __shfl_xor(static_cast<unsigned long long>(v), static_cast<int>(d), 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// Record r's extent and class.  cls: 0 nothing to walk (beyond n, or out of
-// range), 1 lane, 2 wave.
-__device__ __forceinline__ uint32_t vd_classify(const VdArgs &A, uint64_t r, uint64_t n, uint64_t *off, uint64_t *len,
-                                                uint32_t *status) {
-    *off = 0;
-    *len = 0;
-    *status = LV_VE_OK;
-    if (r >= n) return 0;
-    const uint64_t o = A.rec_off[r], l = A.rec_len[r];
-    if (!extent_ok(o, l, A.payload_bytes)) {
-        *status = LV_VE_OUT_OF_RANGE;
-        return 0;
-    }
-    *off = o;
-    *len = l;
-    return l <= kVdSmall ? 1u : 2u;
-}
-
 // Kernel 0 (one thread): the head.  A kernel, not a memset: a memset node inside a longer captured
 // graph does not replay reliably (DESIGN, mt_init), and a chain of kernels does.
 __global__ void vd_init(VdHead *h) { *h = VdHead{}; }
@@ -378,10 +215,10 @@ __global__ void vd_init(VdHead *h) { *h = VdHead{}; }
 // consecutive records of it: every lane walks its own if it is small, then the
 // wave walks the large ones among them one after another.
 __global__ __launch_bounds__(kVdThreads) void vd_count(const VdArgs A) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[kVdWaves][kVdWindow + kVdWinPad];
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[kVdWaves][kVdWindow + kWinPad];
     __shared__ unsigned long long s_sum[3], s_fb, s_lh[5];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint64_t n = vd_records(A);
+    const uint64_t n = records_to_walk(A.records, A.upstream, A.rec_cap);
     const uint64_t tile = blockIdx.x;
     if (tile * kVdTile >= n) return;  // the whole workgroup
     if (tid < 3) s_sum[tid] = 0;
@@ -390,25 +227,22 @@ __global__ __launch_bounds__(kVdThreads) void vd_count(const VdArgs A) {
     __syncthreads();
     const uint64_t r = tile * kVdTile + tid;
     uint64_t off, len;
-    uint32_t status;
-    const uint32_t cls = vd_classify(A, r, n, &off, &len, &status);
+    const uint32_t cls = record_class<kVdSmall>(A.rec_off, A.rec_len, A.payload_bytes, r, n, &off, &len);
     VdRes res{};
-    res.e.status = status;
-    if (cls == 1) {
-        VdLaneSrc src(A.payload);
-        VdNoSink sink;
-        res = vd_walk(src, sink, off, len);
-    }
-    uint64_t m = __ballot(cls == 2);
-    while (m) {  // wave-uniform
-        const uint32_t b = static_cast<uint32_t>(__builtin_ctzll(m));
-        m &= m - 1;
-        const uint64_t woff = vd_shfl64(off, b), wlen = vd_shfl64(len, b);
-        VdWaveSrc src(A.payload, s_win[wave], woff + wlen, lane);
-        VdNoSink sink;
-        const VdRes wr = vd_walk(src, sink, woff, wlen);
-        if (lane == b) res = wr;
-    }
+    res.e.status = cls == kRecOutOfRange ? LV_VE_OUT_OF_RANGE : LV_VE_OK;
+    dispatch(
+        cls, off, len,
+        [&] {
+            LaneSrc src(A.payload);
+            VdNoSink sink;
+            res = vd_walk(src, sink, off, len);
+        },
+        [&](uint32_t b, uint64_t woff, uint64_t wlen) {
+            WaveSrc<kVdWindow, kVdRound> src(A.payload, s_win[wave], woff + wlen, lane);
+            VdNoSink sink;
+            const VdRes wr = vd_walk(src, sink, woff, wlen);
+            if (lane == b) res = wr;
+        });
     const bool live = r < n, bad = live && res.e.status != LV_VE_OK;
     if (live) {
         A.edits[r] = res.e;
@@ -416,9 +250,9 @@ __global__ __launch_bounds__(kVdThreads) void vd_count(const VdArgs A) {
         A.cnt[3 * r + 1] = res.nd;
         A.cnt[3 * r + 2] = res.np;
     }
-    const uint64_t sf = vd_wave_sum(live ? res.nf : 0), sd = vd_wave_sum(live ? res.nd : 0),
-                   sp = vd_wave_sum(live ? res.np : 0), sb = vd_wave_sum(bad ? 1 : 0);
-    const uint64_t fb = vd_wave_min(bad ? r : ~0ull);
+    const uint64_t sf = wave_sum(live ? res.nf : 0), sd = wave_sum(live ? res.nd : 0),
+                   sp = wave_sum(live ? res.np : 0), sb = wave_sum(bad ? 1 : 0);
+    const uint64_t fb = wave_min(bad ? r : ~0ull);
     if (lane == 0) {
         if (sf) atomicAdd(&s_sum[0], static_cast<unsigned long long>(sf));
         if (sd) atomicAdd(&s_sum[1], static_cast<unsigned long long>(sd));
@@ -430,7 +264,7 @@ __global__ __launch_bounds__(kVdThreads) void vd_count(const VdArgs A) {
     const bool before = live && r < s_fb;
 #pragma unroll
     for (uint32_t b = 0; b < 5; ++b) {
-        const uint64_t v = vd_wave_max(before && ((res.e.has >> b) & 1u) ? r + 1 : 0);
+        const uint64_t v = wave_max(before && ((res.e.has >> b) & 1u) ? r + 1 : 0);
         if (lane == 0 && v) atomicMax(&s_lh[b], static_cast<unsigned long long>(v));
     }
     __syncthreads();
@@ -443,7 +277,7 @@ __global__ __launch_bounds__(kVdThreads) void vd_count(const VdArgs A) {
 // the first bad record and last_has over the tiles; the totals and the status.
 __global__ __launch_bounds__(64) void vd_tiles(const VdArgs A) {
     const uint32_t lane = threadIdx.x;
-    const uint64_t n = vd_records(A);
+    const uint64_t n = records_to_walk(A.records, A.upstream, A.rec_cap);
     const uint64_t tiles = (n + kVdTile - 1) / kVdTile;
     uint64_t sum[3];
 #pragma unroll
@@ -453,7 +287,7 @@ __global__ __launch_bounds__(64) void vd_tiles(const VdArgs A) {
         const uint64_t v = A.tinfo[6 * t];
         fb = v < fb ? v : fb;
     }
-    fb = vd_wave_min(fb);
+    fb = wave_min(fb);
     // tiles before the first bad record's hold no bad record: their last-with-bit is the whole tile's
     const uint64_t upto = fb == ~0ull ? tiles : fb / kVdTile + 1;
     uint64_t lh[5] = {0, 0, 0, 0, 0};
@@ -464,7 +298,7 @@ __global__ __launch_bounds__(64) void vd_tiles(const VdArgs A) {
             lh[b] = v > lh[b] ? v : lh[b];
         }
 #pragma unroll
-    for (uint32_t b = 0; b < 5; ++b) lh[b] = vd_wave_max(lh[b]);
+    for (uint32_t b = 0; b < 5; ++b) lh[b] = wave_max(lh[b]);
     if (lane == 0) {
         uint64_t status = 0;
         const bool up = A.upstream && *A.upstream;
@@ -497,7 +331,7 @@ __global__ __launch_bounds__(64) void vd_tiles(const VdArgs A) {
 // Kernel 3: the emit walk.  The scan of the tile's counts gives each record's
 // three bases; the records with rows are walked again, as in vd_count.
 __global__ __launch_bounds__(kVdThreads) void vd_emit(const VdArgs A) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[kVdWaves][kVdWindow + kVdWinPad];
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[kVdWaves][kVdWindow + kWinPad];
     __shared__ uint64_t s_scan[3 * kVdTile];
     if (A.head->status) return;  // only the totals are written
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -517,29 +351,26 @@ __global__ __launch_bounds__(kVdThreads) void vd_emit(const VdArgs A) {
 #pragma unroll
     for (uint32_t k = 0; k < 3; ++k) base[k] = A.tsum[3 * tile + k] + s_scan[3 * tid + k] - c[k];
     uint64_t off, len;
-    uint32_t status;
-    uint32_t cls = vd_classify(A, r, n, &off, &len, &status);
+    uint32_t cls = record_class<kVdSmall>(A.rec_off, A.rec_len, A.payload_bytes, r, n, &off, &len);
     if (r < n) {
         A.out.d_rec_file[r] = base[0];
         A.out.d_rec_deleted[r] = base[1];
         A.out.d_rec_pointer[r] = base[2];
         A.out.d_edits[r] = A.edits[r];
     }
-    if (!(c[0] | c[1] | c[2])) cls = 0;  // nothing to write
-    if (cls == 1) {
-        VdLaneSrc src(A.payload);
-        VdSink sink{A.out, base[0], base[1], base[2], 0, 0};
-        vd_walk(src, sink, off, len);
-    }
-    uint64_t m = __ballot(cls == 2);
-    while (m) {  // wave-uniform
-        const uint32_t b = static_cast<uint32_t>(__builtin_ctzll(m));
-        m &= m - 1;
-        const uint64_t woff = vd_shfl64(off, b), wlen = vd_shfl64(len, b);
-        VdWaveSrc src(A.payload, s_win[wave], woff + wlen, lane);
-        VdSink sink{A.out, vd_shfl64(base[0], b), vd_shfl64(base[1], b), vd_shfl64(base[2], b), lane, 63u};
-        vd_walk(src, sink, woff, wlen);
-    }
+    if (!(c[0] | c[1] | c[2])) cls = kRecNone;  // nothing to write
+    dispatch(
+        cls, off, len,
+        [&] {
+            LaneSrc src(A.payload);
+            VdSink sink{A.out, base[0], base[1], base[2], 0, 0};
+            vd_walk(src, sink, off, len);
+        },
+        [&](uint32_t b, uint64_t woff, uint64_t wlen) {
+            WaveSrc<kVdWindow, kVdRound> src(A.payload, s_win[wave], woff + wlen, lane);
+            VdSink sink{A.out, shfl64(base[0], b), shfl64(base[1], b), shfl64(base[2], b), lane, 63u};
+            vd_walk(src, sink, woff, wlen);
+        });
 }
 
 // ============================ encode ========================================
@@ -574,20 +405,6 @@ struct VeArgs {
     uint64_t *tkey;  // [tiles] the tiles' comparator and key bytes
 };
 
-__device__ __forceinline__ uint32_t ve_varint_len(uint64_t v) {
-    uint32_t n = 1;
-    for (; v >= 128; v >>= 7) ++n;
-    return n;
-}
-__device__ __forceinline__ uint8_t *ve_put_varint(uint8_t *p, uint64_t v) {
-    while (v >= 128) {
-        *p++ = static_cast<uint8_t>(v | 0x80);
-        v >>= 7;
-    }
-    *p++ = static_cast<uint8_t>(v);
-    return p;
-}
-
 __device__ __forceinline__ uint32_t ve_kind(const VeArgs &A, uint64_t item) {
     return (item >= A.seg[1]) + (item >= A.seg[2]) + (item >= A.seg[3]);
 }
@@ -613,20 +430,6 @@ __device__ __forceinline__ uint64_t ve_rec_off(const VeArgs &A, uint64_t r) {
         at += ve_before(A, k, b[r]) - ve_before(A, k, b[0]);
     }
     return at;
-}
-
-// The record of row i: the r < n with b[r] <= i < b[r + 1] (it exists).  Empty
-// records make equal bounds: the last of them whose bound is <= i is the one.
-__device__ __forceinline__ uint64_t ve_record_of(const uint64_t *b, uint64_t i, uint64_t n) {
-    uint64_t lo = 0, hi = n - 1;
-    for (uint32_t it = 0; it < 33 && lo < hi; ++it) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;  // in (lo, hi]
-        if (b[mid] <= i)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
 }
 
 // Kernel 0 (one thread): the head (a kernel, not a memset: see vd_init).
@@ -685,32 +488,32 @@ __global__ __launch_bounds__(kVeThreads) void ve_size(const VeArgs A) {
                 const bool cmp = e.has & LV_VE_HAS_COMPARATOR;
                 ok = !(e.has & ~LV_VE_HAS_ALL) && (!cmp || extent_ok(e.comparator_off, e.comparator_len, A.src_bytes));
                 if (cmp) {
-                    v += 1 + ve_varint_len(e.comparator_len) + static_cast<uint64_t>(e.comparator_len);
+                    v += 1 + varint_len(e.comparator_len) + static_cast<uint64_t>(e.comparator_len);
                     kb += e.comparator_len;
                 }
-                if (e.has & LV_VE_HAS_LOG_NUMBER) v += 1 + ve_varint_len(e.log_number);
-                if (e.has & LV_VE_HAS_PREV_LOG_NUMBER) v += 1 + ve_varint_len(e.prev_log_number);
-                if (e.has & LV_VE_HAS_NEXT_FILE) v += 1 + ve_varint_len(e.next_file_number);
-                if (e.has & LV_VE_HAS_LAST_SEQUENCE) v += 1 + ve_varint_len(e.last_sequence);
+                if (e.has & LV_VE_HAS_LOG_NUMBER) v += 1 + varint_len(e.log_number);
+                if (e.has & LV_VE_HAS_PREV_LOG_NUMBER) v += 1 + varint_len(e.prev_log_number);
+                if (e.has & LV_VE_HAS_NEXT_FILE) v += 1 + varint_len(e.next_file_number);
+                if (e.has & LV_VE_HAS_LAST_SEQUENCE) v += 1 + varint_len(e.last_sequence);
             } else if (kind == LV_VE_KIND_POINTER) {
                 const lv_ve_pointer q = A.in.d_pointers[i];
                 ok = q.level < LV_VE_NUM_LEVELS && extent_ok(q.key_off, q.key_len, A.src_bytes);
-                v = 2 + ve_varint_len(q.key_len) + static_cast<uint64_t>(q.key_len);
+                v = 2 + varint_len(q.key_len) + static_cast<uint64_t>(q.key_len);
                 kb += q.key_len;
             } else if (kind == LV_VE_KIND_DELETED) {
                 const lv_ve_deleted d = A.in.d_deleted[i];
                 ok = d.level < LV_VE_NUM_LEVELS;
-                if (ok && i > lo && b[ve_record_of(b, i, n)] != i) {  // not its record's first row
+                if (ok && i > lo && b[record_of(b, i, 0, n - 1)] != i) {  // not its record's first row
                     const lv_ve_deleted q = A.in.d_deleted[i - 1];
                     ok = q.level < d.level || (q.level == d.level && q.number < d.number);
                 }
-                v = 2 + ve_varint_len(d.number);
+                v = 2 + varint_len(d.number);
             } else {
                 const lv_ve_file f = A.in.d_files[i];
                 ok = f.level < LV_VE_NUM_LEVELS && extent_ok(f.smallest_off, f.smallest_len, A.src_bytes) &&
                      extent_ok(f.largest_off, f.largest_len, A.src_bytes);
-                v = 2 + ve_varint_len(f.number) + ve_varint_len(f.file_size) + ve_varint_len(f.smallest_len) +
-                    ve_varint_len(f.largest_len) + static_cast<uint64_t>(f.smallest_len) + f.largest_len;
+                v = 2 + varint_len(f.number) + varint_len(f.file_size) + varint_len(f.smallest_len) +
+                    varint_len(f.largest_len) + static_cast<uint64_t>(f.smallest_len) + f.largest_len;
                 kb += static_cast<uint64_t>(f.smallest_len) + f.largest_len;
             }
             if (!ok) atomicMax(&A.head->bad_item, ~((static_cast<unsigned long long>(kind) << 60) | i));
@@ -725,7 +528,7 @@ __global__ __launch_bounds__(kVeThreads) void ve_size(const VeArgs A) {
         const uint32_t j = tid + k * kVeThreads;
         A.pre[base + j] = s[j] - own[k];
     }
-    kb = vd_wave_sum(kb);  // (every lane is here)
+    kb = wave_sum(kb);  // (every lane is here)
     if (lane == 0) s_key[tid >> 6] = kb;
     __syncthreads();
     if (tid == 0) {
@@ -760,13 +563,13 @@ __global__ __launch_bounds__(64) void ve_carry(const VeArgs A) {
         t.records = n;
         t.bad_kind = v >> 60;
         t.bad_row = v & ((1ull << 60) - 1);
-        t.bad_record = t.bad_kind ? ve_record_of(ve_bounds(A, static_cast<uint32_t>(t.bad_kind)), t.bad_row, n) : t.bad_row;
+        t.bad_record = t.bad_kind ? record_of(ve_bounds(A, static_cast<uint32_t>(t.bad_kind)), t.bad_row, 0, n - 1) : t.bad_row;
     } else if (n) {
         const uint64_t tiles = A.seg[4] / kVeTile;
         t.out_bytes = carry_scan(A.tsum, 1, tiles, lane);
         uint64_t kb = 0;
         for (uint64_t i = lane; i < tiles; i += 64) kb += A.tkey[i];
-        t.key_bytes = vd_wave_sum(kb);
+        t.key_bytes = wave_sum(kb);
         t.records = n;
         t.files = A.in.d_rec_file[n] - A.in.d_rec_file[0];
         t.deleted = A.in.d_rec_deleted[n] - A.in.d_rec_deleted[0];
@@ -804,7 +607,7 @@ __global__ __launch_bounds__(kVeThreads) void ve_emit(const VeArgs A) {
             uint8_t *p = A.out.d_out + off;
             if (e.has & LV_VE_HAS_COMPARATOR) {
                 *p++ = 1;
-                p = ve_put_varint(p, e.comparator_len);
+                p = put_varint(p, e.comparator_len);
                 d0 = p;
                 s0 = A.src + e.comparator_off;
                 n0 = e.comparator_len;
@@ -812,22 +615,22 @@ __global__ __launch_bounds__(kVeThreads) void ve_emit(const VeArgs A) {
             }
             if (e.has & LV_VE_HAS_LOG_NUMBER) {
                 *p++ = 2;
-                p = ve_put_varint(p, e.log_number);
+                p = put_varint(p, e.log_number);
             }
             if (e.has & LV_VE_HAS_PREV_LOG_NUMBER) {
                 *p++ = 9;
-                p = ve_put_varint(p, e.prev_log_number);
+                p = put_varint(p, e.prev_log_number);
             }
             if (e.has & LV_VE_HAS_NEXT_FILE) {
                 *p++ = 3;
-                p = ve_put_varint(p, e.next_file_number);
+                p = put_varint(p, e.next_file_number);
             }
             if (e.has & LV_VE_HAS_LAST_SEQUENCE) {
                 *p++ = 4;
-                p = ve_put_varint(p, e.last_sequence);
+                p = put_varint(p, e.last_sequence);
             }
         } else {
-            const uint64_t r = ve_record_of(b, i, n);
+            const uint64_t r = record_of(b, i, 0, n - 1);
             // the record, its scalar group, the kinds before this one, the rows of this kind before this one
             uint64_t at = ve_rec_off(A, r) + ve_before(A, LV_VE_KIND_EDIT, r + 1) - ve_before(A, LV_VE_KIND_EDIT, r);
             if (kind > LV_VE_KIND_POINTER) at += ve_rows(A, LV_VE_KIND_POINTER, r);
@@ -838,7 +641,7 @@ __global__ __launch_bounds__(kVeThreads) void ve_emit(const VeArgs A) {
                 const lv_ve_pointer q = A.in.d_pointers[i];
                 *p++ = 5;
                 *p++ = static_cast<uint8_t>(q.level);
-                p = ve_put_varint(p, q.key_len);
+                p = put_varint(p, q.key_len);
                 d0 = p;
                 s0 = A.src + q.key_off;
                 n0 = q.key_len;
@@ -846,19 +649,19 @@ __global__ __launch_bounds__(kVeThreads) void ve_emit(const VeArgs A) {
                 const lv_ve_deleted d = A.in.d_deleted[i];
                 *p++ = 6;
                 *p++ = static_cast<uint8_t>(d.level);
-                p = ve_put_varint(p, d.number);
+                p = put_varint(p, d.number);
             } else {
                 const lv_ve_file f = A.in.d_files[i];
                 *p++ = 7;
                 *p++ = static_cast<uint8_t>(f.level);
-                p = ve_put_varint(p, f.number);
-                p = ve_put_varint(p, f.file_size);
-                p = ve_put_varint(p, f.smallest_len);
+                p = put_varint(p, f.number);
+                p = put_varint(p, f.file_size);
+                p = put_varint(p, f.smallest_len);
                 d0 = p;
                 s0 = A.src + f.smallest_off;
                 n0 = f.smallest_len;
                 p += n0;
-                p = ve_put_varint(p, f.largest_len);
+                p = put_varint(p, f.largest_len);
                 d1 = p;
                 s1 = A.src + f.largest_off;
                 n1 = f.largest_len;

@@ -27,7 +27,10 @@
 //
 // A wave takes 64 consecutive records at a time: each lane walks its own if it
 // is small, then the wave walks the large ones among them one after another.
-// All position arithmetic is u64.
+// All position arithmetic is u64.  The two byte sources, the varint read, a
+// record's class and the wave's dispatch are lvk/records.h's (LaneSrc,
+// WaveSrc, varint32, record_class, dispatch), which version_edit.hip's decode
+// uses too; the wave reductions are lvk/stage.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,7 +40,7 @@
 #include "../../include/lvgpu/write_batch.h"
 #include "lv_internal.h"
 #include "lvh.h"
-#include "lvk/stage.h"
+#include "lvk/records.h"
 
 namespace lvk {
 
@@ -49,9 +52,7 @@ constexpr uint32_t kWbChunks = kWbTile / 64;          // 64-record chunks of a t
 constexpr uint32_t kWbSmall = 16384;                  // records up to this many bytes: one lane each
 constexpr uint32_t kWbWindow = 4096;                  // LDS window of a wave-class record, bytes
 constexpr uint32_t kWbRound = 64 * 16;                // one load of the wave: 64 lanes x 16 B
-constexpr uint32_t kWbWinPad = 16;                    // LDS behind a window: the 12-byte register refill may run into it
 constexpr uint32_t kWbScanThreads = 1024;             // wb_tiles' one workgroup
-static_assert(kWbWindow % kWbRound == 0 && kWbWindow > kWbRound, "a window is whole rounds, more than one");
 static_assert(kWbSmall >= LV_WB_HEADER_SIZE, "the lane class takes whole headers");
 
 // What the count pass keeps of the whole batch (workspace, zeroed by the
@@ -72,98 +73,6 @@ struct WbArgs {
     uint64_t *cnt;     // ops of each record
     uint32_t *st;      // status of each record
     uint64_t *tsum;    // ops of each tile, then (wb_tiles) the ops before it
-};
-
-// Records to walk: none when upstream wrote no arrays or the arrays are too
-// short for what it counted.
-__device__ __forceinline__ uint64_t wb_records(const WbArgs &A) {
-    if (A.upstream && *A.upstream) return 0;
-    const uint64_t n = *A.records;
-    return n > A.rec_cap ? 0ull : n;
-}
-
-// ---- byte sources ---------------------------------------------------------
-// One lane: the aligned granule under the last byte asked for, in registers.
-struct WbLaneSrc {
-    const uint8_t *p;
-    uint64_t gi;
-    u32x4 g;
-    __device__ __forceinline__ explicit WbLaneSrc(const uint8_t *payload) : p(payload), gi(~0ull), g{0, 0, 0, 0} {}
-    __device__ __forceinline__ uint32_t byte(uint64_t a) {
-        const uint64_t addr = reinterpret_cast<uint64_t>(p) + a;
-        const uint64_t q = addr >> 4;
-        if (q != gi) {
-            g = *reinterpret_cast<const u32x4 *>(q << 4);
-            gi = q;
-        }
-        const uint32_t i = static_cast<uint32_t>(addr) & 15u;
-        const uint32_t w = i < 8 ? (i < 4 ? g.x : g.y) : (i < 12 ? g.z : g.w);
-        return (w >> (8 * (i & 3u))) & 0xffu;
-    }
-};
-
-// One wave: a window of kWbWindow bytes in LDS, from an aligned address.  A
-// window opens where the parser lands after a skip, with its first round
-// (kWbRound bytes: an entry's header after a long value is all that is wanted
-// of it); when the walk runs on past that round, the rest of the window is
-// loaded at once.  Only granules that begin before the record's end are loaded
-// (the rest read as 0 and are never asked for), so nothing is read past the
-// granule that holds the record's last byte.  Every call is wave-uniform.
-struct WbWaveSrc {
-    const uint8_t *p;
-    uint8_t *lds;
-    uint64_t lo, end;  // window start address (16-B aligned; ~0: none), record end address
-    uint32_t have;     // bytes of the window that are loaded
-    uint32_t lane;
-    // the rn (<= 8) bytes from address ra on, in a register pair: an entry's
-    // header is parsed from it, so the LDS round trip is paid once per header,
-    // not once per byte
-    uint64_t ra, rw;
-    uint32_t rn;
-    __device__ __forceinline__ WbWaveSrc(const uint8_t *payload, uint8_t *window, uint64_t rec_end, uint32_t l)
-        : p(payload), lds(window), lo(~0ull), end(reinterpret_cast<uint64_t>(payload) + rec_end), have(0), lane(l),
-          ra(0), rw(0), rn(0) {}
-    __device__ __forceinline__ void load(uint32_t from, uint32_t to) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // the reads of the old window are done
-        for (uint32_t slot = from / 16 + lane; slot < to / 16; slot += 64) {
-            const uint64_t ga = lo + static_cast<uint64_t>(slot) * 16;
-            u32x4 v{0, 0, 0, 0};
-            if (ga < end) v = *reinterpret_cast<const u32x4 *>(ga);
-            reinterpret_cast<u32x4 *>(lds)[slot] = v;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    __device__ __forceinline__ void refill(uint64_t addr) {
-        if (lo == ~0ull || addr < lo || addr - lo >= kWbWindow) {
-            lo = addr & ~15ull;
-            have = 0;
-        }
-        const uint32_t at = static_cast<uint32_t>(addr - lo);
-        if (at >= have) {  // a new window: its first round; running on: the rest
-            const uint32_t to = have ? kWbWindow : kWbRound;
-            load(have, to);
-            have = to;
-        }
-        // 8 bytes from `at`: three aligned words and a byte shift (the last
-        // may lie in the pad behind the window; only rn bytes are ever used)
-        const uint32_t *w = reinterpret_cast<const uint32_t *>(lds + (at & ~3u));
-        const uint32_t d0 = w[0], d1 = w[1], d2 = w[2], s = at & 3u;
-        const uint32_t l32 = __builtin_amdgcn_alignbyte(d1, d0, s), h32 = __builtin_amdgcn_alignbyte(d2, d1, s);
-        rw = (static_cast<uint64_t>(h32) << 32) | l32;
-        ra = addr;
-        rn = have - at < 8u ? have - at : 8u;
-    }
-    __device__ __forceinline__ uint32_t byte(uint64_t a) {
-        const uint64_t addr = reinterpret_cast<uint64_t>(p) + a;
-        uint64_t d = addr - ra;
-        if (d >= rn) {
-            refill(addr);
-            d = 0;
-        }
-        return static_cast<uint32_t>(rw >> (8u * static_cast<uint32_t>(d))) & 0xffu;
-    }
 };
 
 // ---- op sinks -------------------------------------------------------------
@@ -223,21 +132,9 @@ struct WbRes {
 // [*pos, n): LV_WB_OK with *len and *pos past the length, or the error.
 template <class Src>
 __device__ __forceinline__ uint32_t wb_varstring(Src &src, uint64_t off, uint64_t n, uint64_t *pos, uint32_t *len) {
-    uint32_t result = 0;
-    uint64_t p = *pos;
-    bool done = false;
-    for (uint32_t shift = 0; shift <= 28 && p < n; shift += 7) {
-        const uint32_t b = src.byte(off + p);
-        ++p;
-        result |= (b & 0x7fu) << shift;  // bits above 31 of the fifth byte fall off
-        if (!(b & 0x80u)) {
-            done = true;
-            break;
-        }
-    }
-    if (!done) return LV_WB_BAD_VARINT;
-    if (n - p < result) return LV_WB_BAD_LENGTH;
-    *pos = p;
+    uint32_t result;
+    if (!varint32(src, off, n, pos, &result)) return LV_WB_BAD_VARINT;
+    if (n - *pos < result) return LV_WB_BAD_LENGTH;
     *len = result;
     return LV_WB_OK;
 }
@@ -284,52 +181,6 @@ __device__ __forceinline__ WbRes wb_walk(Src &src, Sink &sink, uint64_t off, uin
     return r;
 }
 
-__device__ __forceinline__ uint64_t wb_shfl64(uint64_t v, uint32_t src) {
-    const uint32_t lo = __shfl(static_cast<uint32_t>(v), static_cast<int>(src));
-    const uint32_t hi = __shfl(static_cast<uint32_t>(v >> 32), static_cast<int>(src));
-    return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
-__device__ __forceinline__ uint64_t wb_wave_sum(uint64_t v) {
-#pragma unroll
-    for (uint32_t d = 32; d; d >>= 1) {
-        const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), static_cast<int>(d));
-        const uint32_t hi = __shfl_xor(static_cast<uint32_t>(v >> 32), static_cast<int>(d));
-        v += (static_cast<uint64_t>(hi) << 32) | lo;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t wb_wave_max(uint64_t v) {
-#pragma unroll
-    for (uint32_t d = 32; d; d >>= 1) {
-        const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), static_cast<int>(d));
-        const uint32_t hi = __shfl_xor(static_cast<uint32_t>(v >> 32), static_cast<int>(d));
-        const uint64_t o = (static_cast<uint64_t>(hi) << 32) | lo;
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// Record r's extent and class.  cls: 0 nothing to walk (beyond n, or out of
-// range), 1 lane, 2 wave.
-__device__ __forceinline__ uint32_t wb_classify(const WbArgs &A, uint64_t r, uint64_t n, uint64_t *off, uint64_t *len,
-                                                uint32_t *status) {
-    *off = 0;
-    *len = 0;
-    *status = LV_WB_OK;
-    if (r >= n) return 0;
-    const uint64_t o = A.rec_off[r], l = A.rec_len[r];
-    // !extent_ok(o, l, payload_bytes), spelled out: through the helper the compares come out inverted
-    // and the walks behind them move by 24 bytes, which measured 1-2 % slower on long records
-    if (o > A.payload_bytes || l > A.payload_bytes - o) {  // u64, no wrap
-        *status = LV_WB_OUT_OF_RANGE;
-        return 0;
-    }
-    *off = o;
-    *len = l;
-    return l <= kWbSmall ? 1u : 2u;
-}
-
 // Workgroup-wide exclusive scan of one u64 per thread (Hillis-Steele in LDS);
 // *total = the sum of all.
 template <uint32_t kThreads>
@@ -353,10 +204,10 @@ __device__ __forceinline__ uint64_t wb_scan(uint64_t v, uint64_t *lds, uint64_t 
 // Kernel 1: the count walk.  A workgroup takes a tile of kWbTile records, its
 // waves the tile's 64-record chunks.
 __global__ __launch_bounds__(kWbThreads) void wb_count(const WbArgs A) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[kWbWaves][kWbWindow + kWbWinPad];
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[kWbWaves][kWbWindow + kWinPad];
     __shared__ unsigned long long s_tile;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint64_t n = wb_records(A);
+    const uint64_t n = records_to_walk(A.records, A.upstream, A.rec_cap);
     const uint64_t ntiles = (n + kWbTile - 1) / kWbTile;
     uint64_t kb = 0, vb = 0, bad = 0, last = 0;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -366,24 +217,21 @@ __global__ __launch_bounds__(kWbThreads) void wb_count(const WbArgs A) {
         for (uint32_t c = wave; c < kWbChunks; c += kWbWaves) {
             const uint64_t r = tile * kWbTile + c * 64u + lane;
             uint64_t off, len;
-            uint32_t status;
-            const uint32_t cls = wb_classify(A, r, n, &off, &len, &status);
-            WbRes res{0, 0, 0, 0, status};
-            if (cls == 1) {
-                WbLaneSrc src(A.payload);
-                WbNoSink sink;
-                res = wb_walk(src, sink, off, len);
-            }
-            uint64_t m = __ballot(cls == 2);
-            while (m) {  // wave-uniform
-                const uint32_t b = static_cast<uint32_t>(__builtin_ctzll(m));
-                m &= m - 1;
-                const uint64_t woff = wb_shfl64(off, b), wlen = wb_shfl64(len, b);
-                WbWaveSrc src(A.payload, s_win[wave], woff + wlen, lane);
-                WbNoSink sink;
-                const WbRes wr = wb_walk(src, sink, woff, wlen);
-                if (lane == b) res = wr;
-            }
+            const uint32_t cls = record_class<kWbSmall>(A.rec_off, A.rec_len, A.payload_bytes, r, n, &off, &len);
+            WbRes res{0, 0, 0, 0, cls == kRecOutOfRange ? LV_WB_OUT_OF_RANGE : LV_WB_OK};
+            dispatch(
+                cls, off, len,
+                [&] {
+                    LaneSrc src(A.payload);
+                    WbNoSink sink;
+                    res = wb_walk(src, sink, off, len);
+                },
+                [&](uint32_t b, uint64_t woff, uint64_t wlen) {
+                    WaveSrc<kWbWindow, kWbRound> src(A.payload, s_win[wave], woff + wlen, lane);
+                    WbNoSink sink;
+                    const WbRes wr = wb_walk(src, sink, woff, wlen);
+                    if (lane == b) res = wr;
+                });
             if (r < n) {
                 A.cnt[r] = res.found;
                 A.st[r] = res.status;
@@ -397,16 +245,16 @@ __global__ __launch_bounds__(kWbThreads) void wb_count(const WbArgs A) {
                 }
             }
         }
-        ops = wb_wave_sum(ops);
+        ops = wave_sum(ops);
         if (lane == 0 && ops) atomicAdd(&s_tile, static_cast<unsigned long long>(ops));
         __syncthreads();
         if (tid == 0) A.tsum[tile] = s_tile;
         __syncthreads();
     }
-    kb = wb_wave_sum(kb);
-    vb = wb_wave_sum(vb);
-    bad = wb_wave_sum(bad);
-    last = wb_wave_max(last);
+    kb = wave_sum(kb);
+    vb = wave_sum(vb);
+    bad = wave_sum(bad);
+    last = wave_max(last);
     if (lane == 0) {
         if (kb) atomicAdd(&A.head->key_bytes, static_cast<unsigned long long>(kb));
         if (vb) atomicAdd(&A.head->val_bytes, static_cast<unsigned long long>(vb));
@@ -420,7 +268,7 @@ __global__ __launch_bounds__(kWbThreads) void wb_count(const WbArgs A) {
 __global__ __launch_bounds__(kWbScanThreads) void wb_tiles(const WbArgs A) {
     __shared__ uint64_t s_scan[kWbScanThreads];
     const uint32_t t = threadIdx.x;
-    const uint64_t n = wb_records(A);
+    const uint64_t n = records_to_walk(A.records, A.upstream, A.rec_cap);
     const uint64_t ntiles = (n + kWbTile - 1) / kWbTile;
     uint64_t carry = 0;
     for (uint64_t base = 0; base < ntiles; base += kWbScanThreads) {
@@ -455,7 +303,7 @@ __global__ __launch_bounds__(kWbScanThreads) void wb_tiles(const WbArgs A) {
 // Kernel 3: the emit walk.  The scan of a tile's counts gives each record's
 // base; the records with ops are walked again, as in wb_count.
 __global__ __launch_bounds__(kWbThreads) void wb_emit(const WbArgs A) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[kWbWaves][kWbWindow + kWbWinPad];
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[kWbWaves][kWbWindow + kWinPad];
     __shared__ uint64_t s_scan[kWbThreads];
     __shared__ uint64_t s_base[kWbTile];
     if (A.head->status) return;  // only the totals are written
@@ -485,21 +333,21 @@ __global__ __launch_bounds__(kWbThreads) void wb_emit(const WbArgs A) {
         for (uint32_t ch = wave; ch < kWbChunks; ch += kWbWaves) {
             const uint64_t r = tile * kWbTile + ch * 64u + lane;
             uint64_t off, len;
-            uint32_t status;
-            uint32_t cls = wb_classify(A, r, n, &off, &len, &status);
-            if (cls && A.cnt[r] == 0) cls = 0;  // nothing to write
+            uint32_t cls = record_class<kWbSmall>(A.rec_off, A.rec_len, A.payload_bytes, r, n, &off, &len);
+            if (cls && A.cnt[r] == 0) cls = kRecNone;  // nothing to write
             const uint64_t base = s_base[ch * 64u + lane];
-            if (cls == 1) {
-                WbLaneSrc src(A.payload);
+            // lvk::dispatch, spelled out: through the template this kernel takes 92 VGPRs, not 90 (DESIGN)
+            if (cls == kRecLane) {
+                LaneSrc src(A.payload);
                 WbLaneSink sink{A.out.d_ops, base, A.out.op_cap};
                 wb_walk(src, sink, off, len);
             }
-            uint64_t m = __ballot(cls == 2);
+            uint64_t m = __ballot(cls == kRecWave);
             while (m) {  // wave-uniform
                 const uint32_t b = static_cast<uint32_t>(__builtin_ctzll(m));
                 m &= m - 1;
-                const uint64_t woff = wb_shfl64(off, b), wlen = wb_shfl64(len, b), wbase = wb_shfl64(base, b);
-                WbWaveSrc src(A.payload, s_win[wave], woff + wlen, lane);
+                const uint64_t woff = shfl64(off, b), wlen = shfl64(len, b), wbase = shfl64(base, b);
+                WaveSrc<kWbWindow, kWbRound> src(A.payload, s_win[wave], woff + wlen, lane);
                 WbWaveSink sink{A.out.d_ops, wbase, A.out.op_cap, lane, 0, 0, 0, 0, 0};
                 wb_walk(src, sink, woff, wlen);
             }

@@ -35,7 +35,8 @@
 // record index.  All sizes and positions are u64.  The op loads and stores,
 // the extent check, both levels of the scan and the shared copy are
 // lvk/stage.h's (load_op, store_op, extent_ok, tile_scan, carry_scan,
-// group_copy).
+// group_copy), and so are the wave's sums, the varint store and the search
+// (wave_sum, put_varint, record_of).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -82,36 +83,15 @@ struct WeArgs {
     uint64_t *tkey, *tval;  // [tiles] the tiles' key and value bytes
 };
 
+// lvk::varint_len of a u32 as a compare ladder: with the shared loop we_size grows
+// from 1,269 to 1,297 lines of assembly and from 52 to 55 SGPRs (DESIGN)
 __device__ __forceinline__ uint32_t we_varint_len(uint32_t v) {
     return v < (1u << 7) ? 1u : v < (1u << 14) ? 2u : v < (1u << 21) ? 3u : v < (1u << 28) ? 4u : 5u;
-}
-
-__device__ __forceinline__ uint8_t *we_put_varint(uint8_t *p, uint32_t v) {
-    while (v >= 128) {
-        *p++ = static_cast<uint8_t>(v | 0x80);
-        v >>= 7;
-    }
-    *p++ = static_cast<uint8_t>(v);
-    return p;
 }
 
 // The bytes of all entries before op j (j <= ops; behind we_carry).
 __device__ __forceinline__ uint64_t we_before(const WeArgs &A, uint64_t j, uint64_t nops) {
     return j < nops ? A.pre[j] + A.tsum[j / kWeTile] : A.head->entries;
-}
-
-// The record of op i: the r < n with rec_op[r] <= i < rec_op[r + 1], searched
-// in [lo, hi] (it lies there).  Empty records make equal bounds: the last of
-// them whose bound is <= i is the one.
-__device__ __forceinline__ uint64_t we_record_of(const uint64_t *rec_op, uint64_t i, uint64_t lo, uint64_t hi) {
-    for (uint32_t it = 0; it < 33 && lo < hi; ++it) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;  // in (lo, hi]
-        if (rec_op[mid] <= i)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
 }
 
 // Kernel 1: the record bounds.
@@ -181,11 +161,8 @@ __global__ __launch_bounds__(kWeThreads) void we_size(const WeArgs A) {
         if (j < cnt) A.pre[base + j] = s[j] - own[k];
     }
     // the tile's key and value bytes: the waves' sums (every lane is here), then theirs
-#pragma unroll
-    for (uint32_t d = 32; d; d >>= 1) {
-        kb += __shfl_xor(static_cast<unsigned long long>(kb), static_cast<int>(d), 64);
-        vb += __shfl_xor(static_cast<unsigned long long>(vb), static_cast<int>(d), 64);
-    }
+    kb = wave_sum(kb);
+    vb = wave_sum(vb);
     if (lane == 0) {
         s_kv[0][tid >> 6] = kb;
         s_kv[1][tid >> 6] = vb;
@@ -224,7 +201,7 @@ __global__ __launch_bounds__(64) void we_carry(const WeArgs A) {
         t.status = LV_WB_ENCODE_BAD_OP;
         t.records = n;
         t.bad_op = ~static_cast<uint64_t>(h->bad_op);
-        t.bad_record = we_record_of(A.rec_op, t.bad_op, 0, n - 1);  // (an op of a record: n > 0)
+        t.bad_record = record_of(A.rec_op, t.bad_op, 0, n - 1);  // (an op of a record: n > 0)
     } else {
         const uint64_t nops = n ? A.rec_op[n] - A.rec_op[0] : 0;
         const uint64_t tiles = (nops + kWeTile - 1) / kWeTile;
@@ -234,15 +211,10 @@ __global__ __launch_bounds__(64) void we_carry(const WeArgs A) {
             kb += A.tkey[i];
             vb += A.tval[i];
         }
-#pragma unroll
-        for (uint32_t d = 32; d; d >>= 1) {  // (every lane is here)
-            kb += __shfl_xor(static_cast<unsigned long long>(kb), static_cast<int>(d), 64);
-            vb += __shfl_xor(static_cast<unsigned long long>(vb), static_cast<int>(d), 64);
-        }
         t.records = n;
         t.ops = nops;
-        t.key_bytes = kb;
-        t.value_bytes = vb;
+        t.key_bytes = wave_sum(kb);  // (every lane is here)
+        t.value_bytes = wave_sum(vb);
         t.out_bytes = LV_WB_HEADER_SIZE * n + entries;
         t.last_sequence = A.first_seq - 1 + nops;
         if (t.out_bytes > A.out.out_cap) t.status = LV_WB_ENCODE_OUT_OVER;
@@ -290,7 +262,7 @@ __global__ __launch_bounds__(kWeThreads) void we_emit(const WeArgs A) {
     if (blk >= nops) return;  // the whole workgroup
     if (tid < 2) {
         const uint64_t last = nops - blk < kWeThreads ? nops - 1 : blk + kWeThreads - 1;
-        s_rec[tid] = we_record_of(A.rec_op, first + (tid ? last : blk), 0, n - 1);
+        s_rec[tid] = record_of(A.rec_op, first + (tid ? last : blk), 0, n - 1);
     }
     __syncthreads();
     const uint64_t j = blk + tid;
@@ -301,11 +273,11 @@ __global__ __launch_bounds__(kWeThreads) void we_emit(const WeArgs A) {
         const uint64_t i = first + j;
         const lv_wb_op o = load_op(A.ops + i);
         const uint32_t type = static_cast<uint32_t>(o.tag & 0xffu);
-        const uint64_t r = we_record_of(A.rec_op, i, s_rec[0], s_rec[1]);
+        const uint64_t r = record_of(A.rec_op, i, s_rec[0], s_rec[1]);
         const uint64_t at = LV_WB_HEADER_SIZE * (r + 1) + A.pre[j] + A.tsum[j / kWeTile];
         uint8_t *p = A.out.d_out + at;
         *p++ = static_cast<uint8_t>(type);
-        p = we_put_varint(p, o.key_len);
+        p = put_varint(p, o.key_len);
         lv_wb_op w;
         w.tag = ((A.first_seq + j) << 8) | type;
         w.key_off = static_cast<uint64_t>(p - A.out.d_out);
@@ -317,7 +289,7 @@ __global__ __launch_bounds__(kWeThreads) void we_emit(const WeArgs A) {
         w.val_off = w.key_off + kn;
         w.val_len = 0;
         if (type == LV_WB_TYPE_VALUE) {
-            p = we_put_varint(p, o.val_len);
+            p = put_varint(p, o.val_len);
             w.val_off = static_cast<uint64_t>(p - A.out.d_out);
             w.val_len = o.val_len;
             vd = p;

@@ -175,6 +175,44 @@ def test_decode_lengths_either_side_of_the_class_boundary(gpu):
     assert want[5]["bad_records"] == 0 and want[5]["files"] > 400 and sum(l > VE.VD_SMALL for l in ln) == 4
 
 
+def just_wave_class(k, bad=False):
+    """A record of kVdSmall + 1 bytes with more than 64 rows: the wave class by
+    one byte.  Good: rows of every kind behind a comparator that makes up the
+    length.  bad: 65 deleted rows, an unknown tag, then zeros."""
+    if bad:
+        b = C.encode_to(C.new_edit(deleted=sorted((j % 7, 1000 * k + j) for j in range(65)))) + bytes([8])
+        return b + bytes(VE.VD_SMALL + 1 - len(b))
+    e = C.new_edit(log_number=k, last_sequence=1 << (20 + k % 40),
+                   pointers=[(j % 7, bytes([j + k & 255]) * (8 + j % 3)) for j in range(30 + k % 5)],
+                   deleted=sorted((j % 7, (k << 32) + j) for j in range(70)),
+                   files=[(j % 7, j, (j + k) << 12, bytes([j & 255]) * (8 + j % 4), b"y" * 9) for j in range(25)])
+    e["comparator"] = b"w" * (VE.VD_SMALL + 1 - len(C.encode_to(e)) - 3)  # tag, two length bytes
+    b = C.encode_to(e)
+    assert len(b) == VE.VD_SMALL + 1
+    return b
+
+
+def test_decode_wave_dispatch(gpu):
+    """One wave's 64 records with the wave class at lanes 0, 1, 31 and 63 among
+    lane-class records of a few rows, record 31 failing after its 65th row; then
+    the rest of the tile, and a second tile whose only record is wave class: a
+    wave with one large record and 63 absent ones.  Each lane must keep its own
+    walk's result and lane b the wave's."""
+    import torch
+    recs = [C.encode_to(e) for e in C.random_edits(77, T, max_rows=3)]
+    for i in (0, 1, 63):
+        recs[i] = just_wave_class(i + 1)
+    recs[31] = just_wave_class(31, bad=True)
+    recs.append(just_wave_class(200))
+    assert len(recs) == T + 1 and [i for i, r in enumerate(recs) if len(r) > VE.VD_SMALL] == [0, 1, 31, 63, T]
+    payload, off, ln = C.lay_out(recs, gap=1, lead=2)
+    _, want = check_decode(torch, gpu, payload, off, ln, shift=7)
+    edits, F, D, Pt, bounds, tot = want
+    assert int(edits[31]["status"]) == C.UNKNOWN_TAG and tot["first_bad"] == 31 and tot["bad_records"] == 1
+    assert [int(np.diff(bounds[1])[i]) for i in (0, 1, 31, 63, T)] == [70, 70, 0, 70, 70]
+    assert [int(np.diff(bounds[0])[i]) for i in (0, 1, 31, 63, T)] == [25, 25, 0, 25, 25]
+
+
 @pytest.mark.parametrize("shift", range(16))
 def test_decode_payload_alignments_and_window_edges(gpu, shift):
     """Every payload alignment; a wave-class record of 12-byte deleted rows whose

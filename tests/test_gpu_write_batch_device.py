@@ -141,6 +141,44 @@ def test_skip_and_flush(gpu):
     assert want[3]["bad_records"] == 0
 
 
+def just_wave_class(nops, seed, seq, bad=False):
+    """A record of WB_SMALL + 1 bytes with nops small ops: the wave class by one
+    byte.  A last Put's (skipped) value makes up the length; with bad, an entry
+    whose key length runs past the record stands in its place (BAD_LENGTH after
+    nops ops), then zeros."""
+    head = C.mixed_batch(nops, seed=seed, seq=seq, maxlen=12).bytes()
+    if bad:
+        rep = hdr(seq, nops + 1) + head[12:] + bytes([C.VALUE]) + C.varint(0xFFFFFFFF)
+        return rep + bytes(SMALL + 1 - len(rep))
+    for vbytes in (2, 3):  # of the value's length varint
+        vlen = SMALL + 1 - len(head) - 5 - vbytes  # tag, key length, "pad"
+        if len(C.varint(vlen)) == vbytes:
+            return C.mixed_batch(nops, seed=seed, seq=seq, maxlen=12).put(b"pad", bytes(vlen)).bytes()
+    raise AssertionError(len(head))
+
+
+def test_wave_dispatch(gpu):
+    """One wave's 64 records with the wave class at lanes 0, 1, 31 and 63 among
+    lane-class records of a few ops, record 31 failing after its 65th op; then
+    the rest of the tile, and a second tile whose only record is wave class: a
+    wave with one large record and 63 absent ones.  Every large record has
+    more than 64 ops, so the staged store flushes; each lane must keep its own
+    walk's result and lane b the wave's."""
+    import torch
+    reps = [C.mixed_batch(1 + i % 4, seed=i, seq=50 * i, maxlen=10).bytes() for i in range(T)]
+    for k, i in enumerate((0, 1, 63)):
+        reps[i] = just_wave_class(66 + 3 * k, seed=100 + i, seq=7000 * (k + 1))
+    reps[31] = just_wave_class(65, seed=131, seq=31000, bad=True)
+    reps.append(just_wave_class(70, seed=200, seq=90000))
+    assert len(reps) == T + 1 and [i for i, r in enumerate(reps) if len(r) > SMALL] == [0, 1, 31, 63, T]
+    assert all(len(reps[i]) == SMALL + 1 for i in (0, 1, 31, 63, T))
+    ops, want = check(torch, gpu, *pack(reps, gaps=[i % 3 for i in range(len(reps))]), shift=3)
+    st = want[2].tolist()
+    assert st[31] == C.BAD_LENGTH and st.count(C.OK) == T and want[3]["bad_records"] == 1
+    counts = np.diff(want[1]).tolist()
+    assert counts[31] == 65 and [counts[i] for i in (0, 1, 63, T)] == [67, 70, 73, 71]
+
+
 def test_corner_ops(gpu):
     """Empty keys and values, a 12-byte record with count 0, and records of
     2-byte deletes only, where ops == (len - 12) / 2: the capacity bound."""

@@ -15,11 +15,18 @@ their literals are from a build of the commit before their workspaces were
 carved.  The scan's log sizes lie either side of one 32 KiB block and of one
 workgroup's 64 blocks; decode and encode go on to the largest capacity one
 call takes (entry and fragment indices are 32-bit) and, for decode, one past
-it."""
+it.
+
+The WriteBatch encode and the two VersionEdit stages were pinned when their
+device helpers moved into the shared headers: their literals are from a build
+of the commit before that.  The VersionEdit encode takes four capacities; its
+tile is 1,024 slots of capacity + 1 per table, so each capacity is also taken
+alone either side of 1,023."""
 import pytest
 
 import lvgpu.memtable as MT
 import lvgpu.table as T
+import lvgpu.version_edit as VE
 import lvgpu.wal as LW
 import lvgpu.write_batch as WB
 
@@ -27,6 +34,7 @@ CAPS = (0, 1, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 100000)
 BLOCK_CAPS = (0, 1, 1024, 1025)
 MAX_CAP = 2**32 - 2        # op_cap / rec_cap of one call
 MAX_BLOCK_CAP = 2**32 - 4  # block_cap of one call
+MAX_ENCODE_ROWS = 2**30    # op_cap of a WriteBatch encode, a row capacity of a VersionEdit encode
 
 WB_DECODE = (64, 112, 3152, 3152, 3184, 6224, 6224, 6272, 12384, 12384, 12432, 1203200)
 MT_BUILD = (16, 80, 16336, 16400, 16464, 32720, 32784, 32848, 65488, 65552, 65616, 6400016)
@@ -72,6 +80,10 @@ WAL_SCAN = (
 WAL_DECODE = (32, 240, 6320, 6336, 6384, 12464, 12480, 12528, 24752, 24768, 24944, 2414144)
 WAL_ENCODE = (2100320, 2100464, 2377792, 2378832, 2132336, 2163008, 2163024, 2164208, 2226752, 2226768, 2227952,
               8200416)
+WB_ENCODE = (64, 128, 2160, 2160, 2176, 4208, 4208, 4224, 8304, 8304, 8320, 802416)
+VE_DECODE = (32, 208, 22560, 22640, 22800, 45152, 45232, 45408, 90352, 90432, 90608, 8828192)
+# rec_cap, file_cap, deleted_cap, pointer_cap = CAPS[i], CAPS[i + 1], CAPS[i + 2], CAPS[i + 3] (cyclic)
+VE_ENCODE = (32896, 32896, 32896, 32896, 32896, 32896, 41120, 49312, 845504, 845504, 837280, 829088)
 
 
 def test_write_batch_decode_workspace_bytes():
@@ -112,3 +124,29 @@ def test_wal_decode_workspace_bytes():
 def test_wal_encode_workspace_bytes():
     assert tuple(LW.encode_workspace_bytes(f) for f in CAPS) == WAL_ENCODE
     assert LW.encode_workspace_bytes(2**32 - 1) == 257701193792  # the most fragments of one call
+
+
+def test_write_batch_encode_workspace_bytes():
+    assert tuple(WB.encode_workspace_bytes(c, c) for c in CAPS) == WB_ENCODE
+    assert WB.encode_workspace_bytes(MAX_CAP, 0) == 64  # rec_cap takes no region
+    assert WB.encode_workspace_bytes(0, MAX_ENCODE_ROWS) == WB.encode_workspace_bytes(MAX_CAP, MAX_ENCODE_ROWS) == 8615100480
+    assert WB.encode_workspace_bytes(MAX_CAP + 1, 0) == 0
+    assert WB.encode_workspace_bytes(0, MAX_ENCODE_ROWS + 1) == 0
+
+
+def test_version_edit_decode_workspace_bytes():
+    assert tuple(VE.decode_workspace_bytes(c) for c in CAPS) == VE_DECODE
+    # the size function knows no limit (lv_version_edit_decode_device refuses rec_cap > 2^32 - 2)
+    assert VE.decode_workspace_bytes(MAX_CAP) == 379165081456
+    assert VE.decode_workspace_bytes(MAX_CAP + 1) == 379165081552
+
+
+def test_version_edit_encode_workspace_bytes():
+    n = len(CAPS)
+    assert tuple(VE.encode_workspace_bytes(*(CAPS[(i + j) % n] for j in range(4))) for i in range(n)) == VE_ENCODE
+    for k in range(4):  # each capacity alone: 1,023 + 1 slots fill its tile, 1,024 + 1 take a second
+        assert [VE.encode_workspace_bytes(*(c if j == k else 0 for j in range(4))) for c in (1023, 1024)] == [32896, 41120]
+    limits = (MAX_CAP, MAX_ENCODE_ROWS, MAX_ENCODE_ROWS, MAX_ENCODE_ROWS)
+    assert VE.encode_workspace_bytes(*limits) == 60247007360
+    for k in range(4):
+        assert VE.encode_workspace_bytes(*(v + (j == k) for j, v in enumerate(limits))) == 0
