@@ -198,7 +198,7 @@ int lv_wal_encode_device(const uint8_t *d_payload, uint64_t payload_bytes, const
  * with a call that may run concurrently.  Every argument is checked on the
  * host before any device call (LV_ERR_INVALID, lv_last_error).
  *
- * Stream-ordered, no host synchronisation: one memset and five launches on
+ * Stream-ordered, no host synchronisation: six launches on
  * `stream`, sized by scan_cap (threads beyond *d_count do nothing).  Unlike
  * lv_wal_encode_device the call stages nothing and asks the runtime nothing
  * about the stream's progress, so it may be captured into a HIP graph, once

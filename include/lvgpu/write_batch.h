@@ -132,8 +132,8 @@ uint32_t lv_write_batch_iterate(const uint8_t *rep, size_t n, lv_wb_op *ops, siz
  * granule never leaves a page), and of a record's bytes only the entry
  * headers: keys and values are skipped, not read.
  *
- * Stream-ordered, no host synchronisation, staging or stream queries: one
- * memset and three launches on `stream`, sized by rec_cap (threads beyond
+ * Stream-ordered, no host synchronisation, staging or stream queries: four
+ * launches on `stream`, sized by rec_cap (threads beyond
  * *d_records do nothing).  Like lv_wal_decode_device it may be captured into a
  * HIP graph once the device has been initialised. */
 #define LV_WB_DECODE_UPSTREAM 1u  /* *d_upstream_status != 0: upstream wrote no arrays; decoded as 0 records */
@@ -242,8 +242,8 @@ int lv_write_batch_decode_device(const uint8_t *d_payload, size_t payload_bytes,
  * entries of d_rec_off / d_rec_len, d_ops_out[0, ops) and *d_totals, whatever
  * the inputs say.
  *
- * Stream-ordered, no host synchronisation, staging or stream queries: one
- * memset and five launches on `stream` (three when op_cap == 0), their grids
+ * Stream-ordered, no host synchronisation, staging or stream queries: six
+ * launches on `stream` (four when op_cap == 0), their grids
  * sized by rec_cap and op_cap; threads beyond the device-resident counts do
  * nothing.  A key or value is copied by one group of lanes however long it is
  * (as in lv_sst_build_device): a single very long value is the call's serial

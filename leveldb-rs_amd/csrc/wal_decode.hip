@@ -260,6 +260,14 @@ __device__ __forceinline__ uint64_t dec_count(const DecArgs &A) {
     return n > A.cap ? 0ull : n;  // the scan overflowed: it wrote no entries
 }
 
+// Kernel 0: "none" (2^32 - 1) in every block's first kill, first entry and end
+// entry.  A kernel, not a memset: a memset node inside a longer captured graph does not
+// replay reliably (DESIGN, mt_init), and a chain of kernels does.
+__global__ __launch_bounds__(kDecThreads) void wal_dec_init(uint32_t *p, uint64_t n) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kDecThreads;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kDecThreads + threadIdx.x; i < n; i += stride) p[i] = ~0u;
+}
+
 // Kernel 1: every entry's event, each block's first kill and entry range.
 __global__ __launch_bounds__(kDecThreads) void wal_dec_classify(const DecArgs A) {
     const uint64_t n = dec_count(A);
@@ -668,7 +676,7 @@ uint64_t dec_carve(Carve &C, uint64_t cap, lvk::DecArgs &A) {
     A.head = C.take<lvk::DecHead>(1);
     A.ev = C.take<uint32_t>(cap);
     A.fpos = C.take<uint64_t>(cap);
-    A.fkill = C.take<uint32_t>(3 * A.nb);  // one region, set with one memset: fkill, bfirst, bend
+    A.fkill = C.take<uint32_t>(3 * A.nb);  // one region, set by one launch: fkill, bfirst, bend
     A.bfirst = A.fkill ? A.fkill + A.nb : nullptr;
     A.bend = A.fkill ? A.bfirst + A.nb : nullptr;
     A.tsum = C.take<lvk::DecTileSum>(tiles);
@@ -755,7 +763,9 @@ int lv_wal_decode_device(const uint8_t *d_log, size_t bytes, const uint64_t *d_h
     const uint64_t cus = static_cast<uint64_t>(c->cus > 0 ? c->cus : 1);
     const dim3 b(lvk::kDecThreads);
     if (scan_cap) {
-        LV_HIP(hipMemsetAsync(A.fkill, 0xff, 3 * A.nb * sizeof(uint32_t), s));
+        const uint64_t words = 3 * A.nb;
+        const uint64_t g0 = std::min<uint64_t>((words + lvk::kDecThreads - 1) / lvk::kDecThreads, 8 * cus);
+        hipLaunchKernelGGL(lvk::wal_dec_init, dim3(static_cast<uint32_t>(g0)), b, 0, s, A.fkill, words);
         const uint64_t g1 = lvgpu_internal::wal_classify_grid(scan_cap, cus);
         hipLaunchKernelGGL(lvk::wal_dec_classify, dim3(static_cast<uint32_t>(g1)), b, 0, s, A);
         const uint64_t g2 = lvgpu_internal::wal_tile_grid(scan_cap, cus);

@@ -55,8 +55,8 @@ constexpr uint32_t kWbRound = 64 * 16;                // one load of the wave: 6
 constexpr uint32_t kWbScanThreads = 1024;             // wb_tiles' one workgroup
 static_assert(kWbSmall >= LV_WB_HEADER_SIZE, "the lane class takes whole headers");
 
-// What the count pass keeps of the whole batch (workspace, zeroed by the
-// call's memset), and what wb_tiles adds for wb_emit.
+// What the count pass keeps of the whole batch (workspace, zeroed by
+// wb_init), and what wb_tiles adds for wb_emit.
 struct WbHead {
     unsigned long long key_bytes, val_bytes, bad, last_seq;
     uint64_t n, status, pad[2];
@@ -200,6 +200,10 @@ __device__ __forceinline__ uint64_t wb_scan(uint64_t v, uint64_t *lds, uint64_t 
     __syncthreads();
     return ex;
 }
+
+// Kernel 0 (one thread): the head.  A kernel, not a memset: a memset node inside a longer captured graph does not
+// replay reliably (DESIGN, mt_init), and a chain of kernels does.
+__global__ void wb_init(WbHead *h) { *h = WbHead{}; }
 
 // Kernel 1: the count walk.  A workgroup takes a tile of kWbTile records, its
 // waves the tile's 64-record chunks.
@@ -437,7 +441,7 @@ int lv_write_batch_decode_device(const uint8_t *d_payload, size_t payload_bytes,
     const uint64_t cus = static_cast<uint64_t>(c->cus > 0 ? c->cus : 1);
     const dim3 b(lvk::kWbThreads);
     const uint32_t grid = static_cast<uint32_t>(lvgpu_internal::wb_grid(rec_cap, cus));
-    LV_HIP(hipMemsetAsync(A.head, 0, sizeof(lvk::WbHead), s));
+    hipLaunchKernelGGL(lvk::wb_init, dim3(1), dim3(1), 0, s, A.head);
     if (grid) hipLaunchKernelGGL(lvk::wb_count, dim3(grid), b, 0, s, A);
     hipLaunchKernelGGL(lvk::wb_tiles, dim3(1), dim3(lvk::kWbScanThreads), 0, s, A);
     if (grid) hipLaunchKernelGGL(lvk::wb_emit, dim3(grid), b, 0, s, A);

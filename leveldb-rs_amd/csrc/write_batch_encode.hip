@@ -58,7 +58,7 @@ static_assert(kWeTile % kWeThreads == 0, "a tile is whole rounds of a workgroup"
 static_assert(kWeWaveCopy >= 16, "a wave copy has at least one granule");
 static_assert(kWeCopyLanes >= 16 && 64 % kWeCopyLanes == 0, "a copy's lanes cover a ragged head or tail of 15 bytes");
 
-struct WeHead {  // workspace, zeroed by the call's memset
+struct WeHead {  // workspace, zeroed by we_init
     uint64_t st0;      // we_validate: UPSTREAM or REC_OVER
     uint64_t n;        // the records to encode (0 with st0)
     uint64_t go;       // we_carry: status 0, the outputs are written
@@ -93,6 +93,10 @@ __device__ __forceinline__ uint32_t we_varint_len(uint32_t v) {
 __device__ __forceinline__ uint64_t we_before(const WeArgs &A, uint64_t j, uint64_t nops) {
     return j < nops ? A.pre[j] + A.tsum[j / kWeTile] : A.head->entries;
 }
+
+// Kernel 0 (one thread): the head.  A kernel, not a memset: a memset node inside a longer captured graph does not
+// replay reliably (DESIGN, mt_init), and a chain of kernels does.
+__global__ void we_init(WeHead *h) { *h = WeHead{}; }
 
 // Kernel 1: the record bounds.
 __global__ __launch_bounds__(kWeThreads) void we_validate(const WeArgs A) {
@@ -391,7 +395,7 @@ int lv_write_batch_encode_device(const uint8_t *d_src, size_t src_bytes, const l
     const uint32_t rec_grid =
         static_cast<uint32_t>(rec_cap ? (static_cast<uint64_t>(rec_cap) + lvk::kWeThreads - 1) / lvk::kWeThreads : 1);
     const uint32_t op_grid = static_cast<uint32_t>((static_cast<uint64_t>(op_cap) + lvk::kWeThreads - 1) / lvk::kWeThreads);
-    LV_HIP(hipMemsetAsync(A.head, 0, sizeof(lvk::WeHead), s));
+    hipLaunchKernelGGL(lvk::we_init, dim3(1), dim3(1), 0, s, A.head);
     hipLaunchKernelGGL(lvk::we_validate, dim3(rec_grid), b, 0, s, A);
     if (op_cap) hipLaunchKernelGGL(lvk::we_size, dim3(static_cast<uint32_t>(we_tiles(op_cap))), b, 0, s, A);
     hipLaunchKernelGGL(lvk::we_carry, dim3(1), dim3(64), 0, s, A);

@@ -329,3 +329,69 @@ def test_graph_capture(gpu):
     g.replay()
     torch.cuda.synchronize()
     assert dec.records() == oracle_read(logs[0])[0] and dec.reports() == oracle_read(logs[0])[2]
+
+
+def test_graph_replayed_in_a_longer_chain(gpu):
+    """scan -> decode -> WriteBatch decode captured as one graph and replayed
+    three times over two logs of one length.  The per-block arrays and the
+    WriteBatch decode's head are set by kernels: set by memset nodes, the chain
+    replayed correctly once, and in the second replay the decode handed on 65
+    of 120 records with status 0 (tests/test_gpu_store.py found it)."""
+    import torch
+    import lvgpu.wal as LW
+    import lvgpu.write_batch as WB
+    from write_batch_cases import WriteBatch
+    sets = []
+    for seed in (3, 4):
+        rng = np.random.default_rng(seed)
+        reps, seq = [], 1
+        for _ in range(120):
+            wb = WriteBatch().set_sequence(seq)
+            for _ in range(int(rng.integers(1, 9))):
+                if rng.random() < 0.4:
+                    wb.delete(b"k%02d" % rng.integers(50))
+                else:
+                    wb.put(b"k%02d" % rng.integers(50), bytes(int(rng.integers(0, 30))))
+            seq += wb.count
+            reps.append(bytes(wb.rep))
+        sets.append((reps, seq - 1))
+    size = max(len(oracle_encode(r)) for r, _ in sets) + 200  # both pads take a two-byte varint
+    logs = []
+    for reps, last in sets:  # the same log length: a last record of one put takes up the difference
+        pad = size - len(oracle_encode(reps)) - H - 12 - 1 - 2 - 2
+        reps.append(bytes(WriteBatch().set_sequence(last + 1).put(b"p", b"p" * pad).rep))
+        logs.append(oracle_encode(reps))
+    assert len(logs[0]) == len(logs[1]) == size and size < B
+    cap = size // H + 2
+    d_log = torch.zeros((size + 15) & ~7, dtype=torch.uint8, device=gpu)[:size]
+
+    def run():
+        hdr, crc, info, count = LW.scan_device(d_log, cap)
+        dec = LW.decode_device(d_log, hdr, crc, info, count, fill=CANARY)
+        ops = WB.decode_device(dec.payload, dec.rec_off, dec.rec_len, dec.totals[0:1], dec.totals[4:5], rec_cap=cap)
+        return dec, ops, (hdr, crc, info, count)
+
+    def verify(k, dec, ops, what):
+        torch.cuda.synchronize()
+        dec._tot = ops._tot = None
+        assert dec.records() == sets[k][0] and dec.reports() == [], what
+        t = ops.sync_totals()
+        assert (t["records"], t["bad_records"], t["last_sequence"]) == (121, 0, sets[k][1] + 1), (what, t)
+
+    def load(k):
+        d_log.copy_(torch.frombuffer(bytearray(logs[k]), dtype=torch.uint8))
+    load(0)
+    dec, ops, keep = run()
+    verify(0, dec, ops, "warm-up")
+    s = torch.cuda.Stream(device=gpu)
+    g = torch.cuda.CUDAGraph()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        with torch.cuda.graph(g, stream=s):
+            dec, ops, keep = run()
+    torch.cuda.synchronize()
+    for k in (1, 0, 1):
+        load(k)
+        torch.cuda.synchronize()
+        g.replay()
+        verify(k, dec, ops, f"replay of log {k}")
