@@ -29,7 +29,10 @@
  * the table cache; iterators and range reads over a version; compression.
  * (VersionEdit encode / decode, the record of the MANIFEST:
  * lv_version_edit_decode_device / lv_version_edit_encode_device,
- * version_edit.h.  A compaction's output as a run of tables with their records:
+ * version_edit.h.  Applying decoded edits to the ordered d_files this header
+ * reads (VersionSet::Builder, Recover): lv_version_apply_device,
+ * version_set.h; the CURRENT file, compaction picking, allowed_seeks and the
+ * comparator-name check stay out of scope.  A compaction's output as a run of tables with their records:
  * lv_compact_output_device, compact.h.  Range reads: lv_memtable_range_device,
  * memtable.h, is DBIter's forward walk over a sorted memtable quadruple; for
  * now a version's range goes through lv_sst_scan_device per table, appended,
@@ -221,6 +224,7 @@ typedef struct lv_version_file {         /* 64 bytes, 8-B aligned; FileMetaData 
 #define LV_VERSION_FILE_EMPTY      3u
 #define LV_VERSION_FILE_CORRUPT    4u
 #define LV_VERSION_FILE_BOUND_OVER 5u
+#define LV_VERSION_FILE_UNPLACED   6u    /* lv_version_apply_device (version_set.h): no image placement for the file */
 
 /* (lv_version_state, not lv_version: that name is crc32c.h's version-string function) */
 typedef struct lv_version_state {        /* device memory, 8-B aligned, always written */

@@ -31,10 +31,11 @@
  * twins below.  last_has of the decode totals is the project's own definition
  * (what upstream's VersionSet::Recover keeps); the reference has no VersionSet.
  *
- * Out of scope: applying edits to a version (VersionSet::Builder, Recover,
- * LogAndApply); turning decoded rows into lv_version_file records (those need
- * image placements the manifest does not hold); the CURRENT file; compaction
- * picking.
+ * Applying edits to a version (VersionSet::Builder, Recover), and with it
+ * turning decoded rows into lv_version_file records (the image placements the
+ * manifest does not hold come in as a directory), is lv_version_apply_device,
+ * version_set.h.  Out of scope: the CURRENT file; compaction picking;
+ * allowed_seeks; the comparator-name check.
  *
  * ---- Data ---------------------------------------------------------------------
  *

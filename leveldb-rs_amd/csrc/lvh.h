@@ -2,7 +2,7 @@
 // (blocks.hip, sort.hip, classes.hip, sst.hip, context.hip; the WAL stages
 // wal_scan.hip, wal_encode.hip, wal_decode.hip; the op-table stages
 // write_batch.hip, write_batch_encode.hip, memtable.hip, memtable_range.hip, sst_build.hip, sst_get.hip, sst_scan.hip,
-// compact.hip, version.hip, version_edit.hip):
+// compact.hip, version.hip, version_edit.hip, version_set.hip):
 // lv_last_error plumbing, the per-device context (table images, sort
 // workspaces, piece matrices, host-path staging), the argument checks and
 // workspace carving of the device entry points, and the launchers one

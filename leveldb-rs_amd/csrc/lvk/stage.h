@@ -3,7 +3,7 @@
 // and get (memtable.hip) and range reads (memtable_range.hip), SSTable
 // build (sst_build.hip), get (sst_get.hip) and scan (sst_scan.hip), the
 // compaction filter (compact.hip), VersionEdit decode and encode
-// (version_edit.hip).
+// (version_edit.hip), the version builder (version_set.hip).
 //
 // The stages hand each other an op table (32-byte lv_wb_op entries over a
 // payload or an arena) and are built from the same few parts: an extent check

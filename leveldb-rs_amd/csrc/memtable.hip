@@ -19,8 +19,10 @@
 //                 pairs, from buffer p & 1 to the other.  A workgroup owns one
 //                 output tile: two threads find its merge-path diagonals by
 //                 binary search, the inputs are staged in LDS, every thread
-//                 merges kMtPer outputs and the tile leaves in coalesced
-//                 stores.  A pass whose run width covers *d_n_ops exits.
+//                 merges its share of the outputs and the tile leaves in
+//                 coalesced stores (the network and the tile merge are
+//                 lvk/merge_sort.h's, shared with version_set.hip).  A pass
+//                 whose run width covers *d_n_ops exits.
 //   mt_order      reads the buffer the last effective pass wrote (the parity
 //                 is computed from *d_n_ops), writes d_order and counts the
 //                 distinct user keys by comparing neighbours.
@@ -40,6 +42,7 @@
 #include "lv_internal.h"
 #include "lvh.h"
 #include "lvk/knobs.h"
+#include "lvk/merge_sort.h"
 #include "lvk/stage.h"
 
 namespace lvk {
@@ -48,7 +51,6 @@ constexpr uint32_t kMtTile = LVK_MT_TILE;      // entries per tile (sorted in LD
 constexpr uint32_t kMtPrefix = LVK_MT_PREFIX;  // key bytes held in an entry
 constexpr uint32_t kMtWords = kMtPrefix / 8;
 constexpr uint32_t kMtThreads = 256;
-constexpr uint32_t kMtPer = kMtTile / kMtThreads;  // merge outputs per thread
 constexpr uint32_t kMtNone = 0xffffffffu;          // idx of a padding entry: after every op (op_cap <= 2^32 - 2)
 static_assert(kMtPrefix == 8 || kMtPrefix == 16, "the prefix is one or two 8-byte words");
 static_assert(kMtTile >= kMtThreads && (kMtTile & (kMtTile - 1)) == 0, "a tile is a power of two, a thread's share whole");
@@ -116,6 +118,11 @@ __device__ __forceinline__ bool mt_less(const MtArgs &A, const MtEnt &a, const M
     if (ta != tb) return ta > tb;  // tag descending, unsigned
     return a.idx > b.idx;          // an exact duplicate: the later op first
 }
+// The order as lvk/merge_sort.h takes it.
+struct MtLess {
+    const MtArgs &A;
+    __device__ __forceinline__ bool operator()(const MtEnt &a, const MtEnt &b) const { return mt_less(A, a, b); }
+};
 
 // Kernel 0 (one thread): the head.  A kernel, not a memset: the call is then
 // a chain of kernel launches only, which is also what a captured graph replays.
@@ -171,40 +178,13 @@ __global__ __launch_bounds__(kMtThreads) void mt_tile_sort(const MtArgs A) {
         if (tid == 0) atomicOr(&A.head->bad, 1u);
         return;
     }
-    for (uint32_t k = 2; k <= m; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t t = tid; t < m / 2; t += kMtThreads) {
-                const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                const bool up = (i & k) == 0;
-                const MtEnt a = s[i], b = s[l];
-                if (mt_less(A, b, a) == up) {
-                    s[i] = b;
-                    s[l] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    lds_bitonic_sort<kMtThreads>(s, m, tid, MtLess{A});
     MtEnt *out = A.buf[0];
     for (uint32_t j = tid; j < cnt; j += kMtThreads) out[base + j] = s[j];
 }
 
-// The merge path of diagonal d over the sorted runs a[0, la) and b[0, lb):
-// how many of the first d outputs come from a.  At most 33 steps (la < 2^32).
-__device__ __forceinline__ uint64_t mt_path(const MtArgs &A, const MtEnt *a, uint64_t la, const MtEnt *b, uint64_t lb,
-                                            uint64_t d) {
-    uint64_t lo = d > lb ? d - lb : 0, hi = d < la ? d : la;
-    for (uint32_t it = 0; it < 64 && lo < hi; ++it) {
-        const uint64_t mid = lo + (hi - lo) / 2;  // lo <= mid < hi: mid < la and d - 1 - mid < lb
-        if (mt_less(A, b[d - 1 - mid], a[mid]))
-            hi = mid;
-        else
-            lo = mid + 1;
-    }
-    return lo;
-}
-
-// Kernel 2: one merge pass.  Runs of w = kMtTile << pass entries, in pairs.
+// Kernel 2: one merge pass.  Runs of w = kMtTile << pass entries, in pairs
+// (lvk::merge_tile: merge-path diagonals, the inputs staged in LDS).
 __global__ __launch_bounds__(kMtThreads) void mt_merge(const MtArgs A, uint32_t pass) {
     __shared__ MtEnt s[kMtTile];
     __shared__ uint64_t s_split[2];
@@ -216,44 +196,7 @@ __global__ __launch_bounds__(kMtThreads) void mt_merge(const MtArgs A, uint32_t 
     if (w >= n || o0 >= n || A.head->bad) return;  // one run already, beyond the entries, or no table
     const MtEnt *in = pass & 1u ? A.buf[1] : A.buf[0];
     MtEnt *out = pass & 1u ? A.buf[0] : A.buf[1];
-    const uint64_t start = o0 / (2 * w) * (2 * w);
-    const uint64_t mid = start + w < n ? start + w : n, end = start + 2 * w < n ? start + 2 * w : n;
-    const uint64_t la = mid - start, lb = end - mid;
-    const MtEnt *ra = in + start, *rb = in + mid;
-    const uint64_t d0 = o0 - start, d1 = d0 + kMtTile < la + lb ? d0 + kMtTile : la + lb;
-    if (tid < 2) s_split[tid] = mt_path(A, ra, la, rb, lb, tid ? d1 : d0);
-    __syncthreads();
-    const uint64_t a0 = s_split[0], a1 = s_split[1], b0 = d0 - a0;
-    const uint32_t na = static_cast<uint32_t>(a1 - a0), total = static_cast<uint32_t>(d1 - d0), nb = total - na;
-    for (uint32_t j = tid; j < total; j += kMtThreads) s[j] = j < na ? ra[a0 + j] : rb[b0 + (j - na)];
-    __syncthreads();
-    // this thread's outputs [q0, q1) of the tile: its own diagonal, then a serial merge
-    const uint32_t q0 = tid * kMtPer < total ? tid * kMtPer : total;
-    const uint32_t q1 = q0 + kMtPer < total ? q0 + kMtPer : total;
-    uint32_t x = static_cast<uint32_t>(mt_path(A, s, na, s + na, nb, q0)), y = q0 - x;
-    constexpr uint32_t kQ = sizeof(MtEnt) / 16;  // an entry as 16-B register quads
-    u32x4 r[kMtPer][kQ];
-#pragma unroll
-    for (uint32_t k = 0; k < kMtPer; ++k) {
-        uint32_t from = 0;
-        if (q0 + k < q1) {
-            const bool take_a = y >= nb || (x < na && !mt_less(A, s[na + y], s[x]));
-            from = take_a ? x : na + y;
-            x += take_a;
-            y += !take_a;
-        }
-#pragma unroll
-        for (uint32_t v = 0; v < kQ; ++v) r[k][v] = reinterpret_cast<const u32x4 *>(s + from)[v];
-    }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t k = 0; k < kMtPer; ++k)
-        if (q0 + k < q1) {
-#pragma unroll
-            for (uint32_t v = 0; v < kQ; ++v) reinterpret_cast<u32x4 *>(s + q0 + k)[v] = r[k][v];
-        }
-    __syncthreads();
-    for (uint32_t j = tid; j < total; j += kMtThreads) out[o0 + j] = s[j];
+    merge_tile<kMtTile, kMtThreads>(MtLess{A}, in, out, n, w, o0, s, s_split, tid);
 }
 
 // Kernel 3: d_order and the distinct user keys.

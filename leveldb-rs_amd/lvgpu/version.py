@@ -27,8 +27,9 @@ from .table import BLOOM_FIELDS, TABLE_FIELDS
 
 NUM_LEVELS = 7                # LV_NUM_LEVELS
 MAX_FILES = 1 << 20           # LV_VERSION_MAX_FILES
-FILE_STATUS = {1: "NO_TABLE", 2: "BAD_EXTENT", 3: "EMPTY", 4: "CORRUPT", 5: "BOUND_OVER"}  # LV_VERSION_FILE_*
-FILE_NO_TABLE, FILE_BAD_EXTENT, FILE_EMPTY, FILE_CORRUPT, FILE_BOUND_OVER = FILE_STATUS
+FILE_STATUS = {1: "NO_TABLE", 2: "BAD_EXTENT", 3: "EMPTY", 4: "CORRUPT", 5: "BOUND_OVER",
+               6: "UNPLACED"}  # LV_VERSION_FILE_*; UNPLACED is lv_version_apply_device's (lvgpu.version_set)
+FILE_NO_TABLE, FILE_BAD_EXTENT, FILE_EMPTY, FILE_CORRUPT, FILE_BOUND_OVER, FILE_UNPLACED = FILE_STATUS
 OPEN_STATUS = {1: "UPSTREAM", 2: "BAD_FILE", 4: "BAD_TABLE", 8: "BAD_BOUND", 16: "UNSORTED"}  # LV_VERSION_OPEN_*
 OPEN_UPSTREAM, OPEN_BAD_FILE, OPEN_BAD_TABLE, OPEN_BAD_BOUND, OPEN_UNSORTED = OPEN_STATUS
 FILE_DTYPE = np.dtype([("number", "<u8"), ("file_off", "<u8"), ("file_cap", "<u8"), ("smallest_off", "<u8"),
